@@ -15,16 +15,26 @@ A step = one tick (one heartbeat interval at a fixed clock): the heartbeat patch
 of every managed node, the lock check of every node, the re-evaluation of
 every pod, ipPool bookkeeping and the host collecting the tick's result, with
 all state resident in HBM.  Steps are queued (kwok_tick_submit for tick k+1
-before kwok_tick_collect of tick k).  Reported beside `value`:
+before kwok_tick_collect of tick k).
+
+A plain run sets up the fleet, runs the warmup steps (the first is the initial
+tick), times the steps and prints the result line.  --dump-outputs DIR then
+writes what the last timed step handed back (dump_outputs) as DIR/<name>.npy;
+the fleet, the clock and the sample are fixed, so two builds can be compared
+file for file.  --full reports beside `value`:
   * the same steps one blocking kwok_tick each;
   * the same steps with the per-tick hand-off a Go caller consumes
     (kwok_read_outputs, KWOK_READ_HEARTBEAT_ONCE: one heartbeat body + the
     patch region + the delete list; the heartbeat handle list only when its
     epoch changes) - PCIe-inclusive;
-  * the initial tick (1M node-init patches + 10M Pending->Running patches with
-    IP allocation), timed on its own, with its own roofline (k_emit).
+  * the k_tick roofline pass, the C4 churn legs on the same engine, the
+    secondary legs (C5 flap, heartbeat-once, C2, emulated ranks: a child
+    process each) and the CPU baseline.
+The initial tick (1M node-init patches + 10M Pending->Running patches with IP
+allocation) is warmup step 0 of every run, timed on its own, with its own
+roofline (k_emit).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N)
 """
 from __future__ import annotations
@@ -87,6 +97,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--nodes-per-rank", type=int, default=NODES_PER_RANK)
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step handed back as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: blocking and hand-off steps, the roofline pass, the churn, "
+                         "flap, heartbeat-once, C2 and emulated-rank legs and the CPU baseline (the options below)")
     ap.add_argument("--cpu-baseline", type=int, default=1, help="time the CPU restatement on rank 0 (N=1)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the all-core leg (0: all cores)")
     ap.add_argument("--cpu-ticks", type=int, default=5)
@@ -854,6 +869,155 @@ class Handoff:
         return out.arena_copied
 
 
+DUMP_LIST = 1 << 19   # entries of a list written whole; longer lists: a seeded sample
+DUMP_BODIES = 2048    # heartbeat bodies written byte for byte
+DUMP_PATCHES = 512    # node-init / pod patches written byte for byte, each kind
+
+
+def dump_outputs(e, res, d):
+    """What the collected tick `res` hands its caller (kwok_read_outputs), as
+    DIR/<name>.npy: float64 for counters, handles and lengths, float32 for bytes;
+    under 64 MB in all.  counters / local_counters: the tick result's.  heartbeat_nodes:
+    every handle in the engine's order; heartbeat_body_sums: the byte sum of every
+    node's heartbeat body, in that order; heartbeat_bodies: DUMP_BODIES bodies byte
+    for byte, the rows heartbeat_rows.  The node-init, pod-patch and delete lists with
+    their lengths / flags (lists over DUMP_LIST entries: the entries <list>_rows), and
+    DUMP_PATCHES patches of each kind byte for byte, back to back in list order.  The
+    samples are drawn with a fixed seed from the list lengths alone.  No file is
+    written for an empty array (a steady tick has no patches and no deletes): the
+    lengths of all lists are in sizes (heartbeats, heartbeat body bytes, node inits,
+    pod patches, deletes)."""
+    os.makedirs(d, exist_ok=True)
+    rng = np.random.default_rng(20240101)
+
+    def rows(n, k):
+        return np.arange(n) if n <= k else np.sort(rng.choice(n, k, replace=False))
+
+    def save(name, x, dt=np.float64):
+        p, x = os.path.join(d, name + ".npy"), np.asarray(x)
+        if x.size:
+            np.save(p, x.astype(dt))
+        elif os.path.exists(p):  # (an earlier dump into the same folder)
+            os.remove(p)
+
+    a = e.read_arrays(res)
+    arena = a["arena"]
+    save("sizes", [res.n_heartbeat, res.heartbeat_len, res.n_node_init, res.n_pod_patch, res.n_delete])
+    save("counters", list(res.counters))
+    save("local_counters", list(res.local_counters))
+    n, ln, st, off = res.n_heartbeat, res.heartbeat_len, int(res.heartbeat_stride), int(a["heartbeat_off"])
+    save("heartbeat_nodes", a["heartbeat_nodes"])
+    if n and off + (n - 1) * st + ln > len(arena):
+        raise RuntimeError("heartbeat bodies outside the copied arena")
+    bodies = np.lib.stride_tricks.as_strided(arena[off:], (n, ln), (st, 1), writeable=False)
+    save("heartbeat_body_sums", bodies.sum(axis=1, dtype=np.uint32))
+    r = rows(n, DUMP_BODIES)
+    save("heartbeat_rows", r)
+    save("heartbeat_bodies", bodies[r], np.float32)
+    for name, hs, offs, lens in (("node_init", a["node_init_nodes"], a["node_init_off"], a["node_init_len"]),
+                                 ("pod_patch", a["pod_patch_pods"], a["pod_patch_off"], a["pod_patch_len"])):
+        r = rows(len(hs), DUMP_LIST)
+        save(name + "_rows", r)
+        save(name + "_handles", hs[r])
+        save(name + "_len", lens[r])
+        r = rows(len(hs), DUMP_PATCHES)
+        save(name + "_patch_rows", r)
+        save(name + "_patches", np.concatenate([arena[int(offs[i]):int(offs[i]) + int(lens[i])] for i in r])
+             if len(r) else np.zeros(0, np.uint8), np.float32)
+    r = rows(len(a["delete_pods"]), DUMP_LIST)
+    save("delete_rows", r)
+    save("delete_pods", a["delete_pods"][r])
+    save("delete_has_finalizers", a["delete_has_finalizers"][r])
+
+
+def full_legs(a, e, fl, pods, now, rank, world, barrier, max_over_ranks, multi, last):
+    """--full, on the headline's engine after its timed steps: the same steps one
+    blocking kwok_tick each and with the per-tick hand-off, the roofline pass and
+    the C4 churn legs.  Returns their entries of the result line."""
+    # ---- the same steps, one blocking kwok_tick each ---------------------------
+    barrier()
+    t1 = time.perf_counter()
+    for k in range(a.steps):
+        e.tick(now, read=False)
+        now += 30
+    barrier()
+    dt_sync = max_over_ranks(time.perf_counter() - t1)
+
+    # ---- the same steps with the per-tick hand-off (queued) --------------------
+    ho = Handoff(e)
+    copied = trans_read = 0
+    barrier()
+    t1 = time.perf_counter()
+    e.tick_submit(now)
+    now += 30
+    for k in range(a.steps):
+        if k + 1 < a.steps:
+            e.tick_submit(now)
+            now += 30
+        r = e.tick_collect(read=False)
+        trans_read += transitions(r.counters)
+        copied += ho.read(r)
+    barrier()
+    dt_read = max_over_ranks(time.perf_counter() - t1)
+
+    # ---- roofline pass: HIP events around each k_tick launch ------------------
+    e.profile_enable(True)
+    for k in range(a.roofline_ticks):
+        e.tick(now, read=False)
+        now += 30
+    phases, nt = e.profile_read()
+    e.profile_enable(False)
+
+    churn = churn_ev = None
+    if a.churn_ticks > 0:
+        now, ch, churn = churn_leg(e, fl, pods, now, a.churn_ticks, a.churn or a.nodes_per_rank, rank, world,
+                                   barrier, max_over_ranks, multi=multi)
+        if world == 1 and not multi:  # the batch with its tick behind it (one call)
+            now, ch, tog = churn_leg(e, fl, pods, now, a.churn_ticks, a.churn or a.nodes_per_rank, ch=ch,
+                                     together=True)
+            churn["together"] = {k: tog[k] for k in ("ms_per_step", "ingest_ms", "tick_ms", "median_ms", "kernel_ms",
+                                                      "value", "unit")}
+            churn["together"]["what"] = ("kwok_ingest_pods_packed12_tick: the tick queued behind the batch's apply "
+                                         "passes, then kwok_tick_collect")
+        if world == 1:  # the same storm through the full record form, beside it
+            now, ch, churn_ev = churn_leg(e, fl, pods, now, max(2, a.churn_ticks // 2), a.churn or a.nodes_per_rank,
+                                          rank, world, barrier, max_over_ranks, packed=False, ch=ch)
+
+    kern_ms = phases["kernel"] / max(nt, 1)
+    classify_ms = phases["classify"] / max(nt, 1)
+    lc = last.local_counters
+    n_nodes, n_pods = lc[8], lc[10]  # nodes_managed, pods_total (this rank)
+    alg_bytes = NODE_BYTES * n_nodes + POD_BYTES * n_pods
+    state_bytes = NODE_STATE_BYTES * n_nodes + POD_BYTES * n_pods
+    achieved = alg_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
+    traffic, traffic_src = stored_pmc(PMC_FILE, "k_tick") if a.nodes_per_rank == NODES_PER_RANK else (None, None)
+    out = {
+        "ms_per_step_kwok_tick": dt_sync / a.steps * 1e3,
+        "ms_per_step_with_handoff": dt_read / a.steps * 1e3,
+        "handoff": {"transitions_per_s": trans_read / dt_read,
+                    "bytes_to_host_per_step": copied / a.steps,
+                    "what": "kwok_read_outputs with KWOK_READ_HEARTBEAT_ONCE (one heartbeat body + patch "
+                            "region + lists; heartbeat handles only when the epoch changes), pageable host "
+                            "buffers, queued ticks"},
+        "phase_ms_per_tick": {k: v / max(nt, 1) for k, v in phases.items()},
+        "roofline": {"bound": "hbm", "kernel": "k_tick", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                     "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                     "bytes_per_launch": alg_bytes, "avg_launch_ms": kern_ms, "traffic_source": traffic_src,
+                     "timing": "HIP events around each k_tick launch (hipExtLaunchKernelGGL), %d ticks" % nt},
+        "state_only": {"bytes_per_tick": state_bytes,
+                       "achieved": state_bytes / (classify_ms * 1e-3) / 1e9 if classify_ms > 0 else 0.0,
+                       "unit": "GB/s", "classify_ms": classify_ms,
+                       "note": "SoA state read + written per tick without the materialised heartbeat bodies, "
+                               "over the classification phase (first chain block start to the last arrival, "
+                               "kernel clock stamps), which runs under the heartbeat stream"},
+    }
+    if churn is not None:
+        out["churn"] = churn
+    if churn_ev is not None:
+        out["churn_events"] = churn_ev
+    return out
+
+
 def main():
     a = parse()
     # stdout carries exactly one JSON line: libraries that print banners to the C
@@ -948,72 +1112,32 @@ def main():
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0)
     host_ms, host_n = e.profile_host(reset=True)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(e, last, a.dump_outputs)
 
-    # ---- the same steps, one blocking kwok_tick each ---------------------------
-    barrier()
-    t1 = time.perf_counter()
-    for k in range(a.steps):
-        e.tick(now, read=False)
-        now += 30
-    barrier()
-    dt_sync = max_over_ranks(time.perf_counter() - t1)
-
-    # ---- the same steps with the per-tick hand-off (queued) --------------------
-    ho = Handoff(e)
-    copied = trans_read = 0
-    barrier()
-    t1 = time.perf_counter()
-    e.tick_submit(now)
-    now += 30
-    for k in range(a.steps):
-        if k + 1 < a.steps:
-            e.tick_submit(now)
-            now += 30
-        r = e.tick_collect(read=False)
-        trans_read += transitions(r.counters)
-        copied += ho.read(r)
-    barrier()
-    dt_read = max_over_ranks(time.perf_counter() - t1)
-
-    # ---- roofline pass: HIP events around each k_tick launch ------------------
-    e.profile_enable(True)
-    for k in range(a.roofline_ticks):
-        e.tick(now, read=False)
-        now += 30
-    phases, nt = e.profile_read()
-    e.profile_enable(False)
-
-    churn = churn_ev = None
-    if a.churn_ticks > 0:
-        now, ch, churn = churn_leg(e, fl, pods, now, a.churn_ticks, a.churn or a.nodes_per_rank, rank, world,
-                                   barrier, max_over_ranks, multi=comm is not None or gather is not None)
-        if world == 1 and comm is None and gather is None:  # the batch with its tick behind it (one call)
-            now, ch, tog = churn_leg(e, fl, pods, now, a.churn_ticks, a.churn or a.nodes_per_rank, ch=ch,
-                                     together=True)
-            churn["together"] = {k: tog[k] for k in ("ms_per_step", "ingest_ms", "tick_ms", "median_ms", "kernel_ms",
-                                                      "value", "unit")}
-            churn["together"]["what"] = ("kwok_ingest_pods_packed12_tick: the tick queued behind the batch's apply "
-                                         "passes, then kwok_tick_collect")
-        if world == 1:  # the same storm through the full record form, beside it
-            now, ch, churn_ev = churn_leg(e, fl, pods, now, max(2, a.churn_ticks // 2), a.churn or a.nodes_per_rank,
-                                          rank, world, barrier, max_over_ranks, packed=False, ch=ch)
-
+    full = full_legs(a, e, fl, pods, now, rank, world, barrier, max_over_ranks,
+                     comm is not None or gather is not None, last) if a.full else {}
     e.close()
-    flap = leg("flap", a) if world == 1 and a.flap_ticks > 0 else None
-    flap_once = leg("flap_once", a) if world == 1 and a.flap_ticks > 0 and a.once_ticks else None
-    hb_once = leg("hb_once", a) if world == 1 and a.once_ticks else None
-    c2 = leg("c2", a) if world == 1 and a.c2 and a.nodes_per_rank == NODES_PER_RANK else None
-    emul = leg("emul", a) if world == 1 and a.emulate_ranks > 1 and not REHEARSAL else None
+    if a.full and world == 1:  # the secondary legs: an engine, and by default a process, of their own
+        flap = leg("flap", a) if a.flap_ticks > 0 else None
+        flap_once = leg("flap_once", a) if a.flap_ticks > 0 and a.once_ticks else None
+        hb_once = leg("hb_once", a) if a.once_ticks else None
+        c2 = leg("c2", a) if a.c2 and a.nodes_per_rank == NODES_PER_RANK else None
+        emul = leg("emul", a) if a.emulate_ranks > 1 and not REHEARSAL else None
+        if flap is not None:
+            full["flap"] = flap
+        if hb_once is not None:
+            if flap_once is not None:
+                hb_once["flap"] = flap_once
+            full["heartbeat_once"] = hb_once
+        if c2 is not None:
+            full["c2"] = c2
+        if emul is not None:
+            full["emulated_ranks"] = emul
+        if a.cpu_baseline:
+            full["cpu_baseline"] = cpu_baseline(a.nodes_per_rank, a.cpu_threads, a.cpu_ticks)
 
     if rank == 0:
-        kern_ms = phases["kernel"] / max(nt, 1)
-        classify_ms = phases["classify"] / max(nt, 1)
-        lc = last.local_counters
-        n_nodes, n_pods = lc[8], lc[10]  # nodes_managed, pods_total (this rank)
-        alg_bytes = NODE_BYTES * n_nodes + POD_BYTES * n_pods
-        state_bytes = NODE_STATE_BYTES * n_nodes + POD_BYTES * n_pods
-        achieved = alg_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
-        traffic, traffic_src = stored_pmc(PMC_FILE, "k_tick") if a.nodes_per_rank == NODES_PER_RANK else (None, None)
         ilc = r0.local_counters
         init_bytes = INIT_BYTES * ilc[1] + POD_PATCH_BYTES * ilc[2]
         emit_ms = ph0["emit_kernel"]
@@ -1024,6 +1148,7 @@ def main():
             "n_gpus": world,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": a.full,
             "ms_per_step": dt / a.steps * 1e3,
             "higher_is_better": True,
             "scaling": "weak",
@@ -1036,15 +1161,7 @@ def main():
                        "nodes_per_gpu": a.nodes_per_rank, "pods_per_node": workload.PODS_PER_NODE,
                        "cidr": cidr, "buckets": workload.BUCKETS, "parallelism": "bucket-sharded x%d" % world},
             "tick_api": "kwok_tick_submit/kwok_tick_collect, tick k+1 queued before tick k is collected",
-            "ms_per_step_kwok_tick": dt_sync / a.steps * 1e3,
-            "ms_per_step_with_handoff": dt_read / a.steps * 1e3,
-            "handoff": {"transitions_per_s": trans_read / dt_read,
-                        "bytes_to_host_per_step": copied / a.steps,
-                        "what": "kwok_read_outputs with KWOK_READ_HEARTBEAT_ONCE (one heartbeat body + patch "
-                                "region + lists; heartbeat handles only when the epoch changes), pageable host "
-                                "buffers, queued ticks"},
             "objects_evaluated_per_s": evald / dt,
-            "phase_ms_per_tick": {k: v / max(nt, 1) for k, v in phases.items()},
             "host_ms_per_tick": {k: v / max(host_n, 1) for k, v in host_ms.items()},
             "initial_tick": {"wall_ms": init_wall * 1e3, "kernel_ms": ph0["kernel"], "emission_ms": emit_ms,
                              "host_ms": init_host,
@@ -1058,35 +1175,10 @@ def main():
                                                "frac": init_bytes / (emit_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
                                                if emit_ms else None}},
             "setup_s": setup_s,
-            "roofline": {"bound": "hbm", "kernel": "k_tick", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "bytes_per_launch": alg_bytes, "avg_launch_ms": kern_ms, "traffic_source": traffic_src,
-                         "timing": "HIP events around each k_tick launch (hipExtLaunchKernelGGL), %d ticks" % nt},
-            "state_only": {"bytes_per_tick": state_bytes,
-                           "achieved": state_bytes / (classify_ms * 1e-3) / 1e9 if classify_ms > 0 else 0.0,
-                           "unit": "GB/s", "classify_ms": classify_ms,
-                           "note": "SoA state read + written per tick without the materialised heartbeat bodies, "
-                                   "over the classification phase (first chain block start to the last arrival, "
-                                   "kernel clock stamps), which runs under the heartbeat stream"},
         }
         if REHEARSAL:
             out["rehearsal"] = "all ranks on GPU 0, host allgather instead of RCCL: not a reported measurement"
-        if churn is not None:
-            out["churn"] = churn
-        if churn_ev is not None:
-            out["churn_events"] = churn_ev
-        if flap is not None:
-            out["flap"] = flap
-        if hb_once is not None:
-            if flap_once is not None:
-                hb_once["flap"] = flap_once
-            out["heartbeat_once"] = hb_once
-        if c2 is not None:
-            out["c2"] = c2
-        if emul is not None:
-            out["emulated_ranks"] = emul
-        if world == 1 and a.cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(a.nodes_per_rank, a.cpu_threads, a.cpu_ticks)
+        out.update(full)
         sys.stdout.flush()
         os.write(json_out, (json.dumps(out) + "\n").encode())
     if world > 1:
