@@ -421,6 +421,11 @@ int kwok_tick(kwok_engine* e, int64_t now_unix, kwok_tick_result* res);
  * engine is destroyed and recreated (state rebuilt from a List, as on restart). */
 int kwok_tick_submit(kwok_engine* e, int64_t now_unix);
 int kwok_tick_collect(kwok_engine* e, kwok_tick_result* res);
+/* A slot's output arena is engine-owned between ticks: the engine keeps the heartbeat
+ * bodies of the slot's previous tick there and may rewrite only the bytes that differ
+ * (KWOK_HB_DELTA=0: every tick writes them all).  Whenever the caller reads it
+ * (kwok_read_outputs, kwok_read_arena, kwok_read_arena_async, kwok_device_outputs), it
+ * holds the complete bodies of the last collected tick; nobody else may write to it. */
 int kwok_read_outputs(kwok_engine* e, kwok_outputs* out);
 /* Bytes [off, off + len) of the last collected tick's output arena (the arena
  * offsets kwok_read_outputs reports without KWOK_READ_HEARTBEAT_ONCE:
@@ -489,6 +494,7 @@ enum { KWOK_STAT_TICKS_FULL = 0 /* ticks run by the full tick kernel (redone tic
        KWOK_STAT_TICKS_ONCE /* heartbeat-once ticks completed by the counting kernel */,
        KWOK_STAT_ONCE_REDO /* counting-kernel ticks that had work and ran again with the full kernel */,
        KWOK_STAT_ONCE_SUMMARY /* counting-kernel launches that read the per-bucket summaries, not the pod rows */,
+       KWOK_STAT_TICKS_HB_DELTA /* ticks whose heartbeat stream rewrote only the lines that changed (KWOK_HB_DELTA) */,
        KWOK_STAT_COUNT };
 int kwok_engine_stats(const kwok_engine* e, uint64_t out[KWOK_STAT_COUNT]);
 

@@ -334,6 +334,23 @@ struct kwok_engine {
         bool rd_pending = false;    //   (a submit or an arena growth that takes the slot waits for it)
         bool no_once = false;       // k_once found work: the tick runs again with k_tick
         bool alloc = false;
+        // What the heartbeat region [0, n x stride) of `arena` provably holds: n complete
+        // bodies of the template generation `gen` at `clock`.  Written by retire alone,
+        // for a tick that completed without error, was not skipped on the device or
+        // requeued, was no k_once tick and ran its stream; cleared by everything that
+        // replaces, poisons or is about to overwrite the arena (grow_arena, alloc_slot,
+        // every enqueue, so also a failed tick and the debug layout-fault tick) and by a
+        // template change.  A tick whose layout matches it exactly writes only the lines
+        // that differ from these bodies (hb_prev).
+        struct HbValid {
+            bool ok = false;
+            const uint8_t* arena = nullptr;
+            uint32_t n = 0, stride = 0, units = 0, gen = 0;
+            uint64_t clock = 0;
+        } hb_valid;
+        uint64_t hb_prev = 0;       // this tick's stream is a delta against the bodies of this clock (0: all bytes)
+        uint32_t hb_n = 0;          // bodies this tick's stream lays out
+        bool hb_record = false;     // retire may record this tick's bodies (not requeued, no layout fault, streamed)
         // the tick in the slot
         int state = 0;  // SLOT_FREE, SLOT_QUEUED (enqueued), SLOT_DONE (finished on the host, not collected)
         uint64_t now = 0, target = 0;
@@ -411,6 +428,8 @@ struct kwok_engine {
     bool results_kernel = false;  // KWOK_INGEST_RESULTS_KERNEL=1: pod batch results written into mapped host arrays by a kernel
     double last_chunk_cut = 0.4;  // KWOK_INGEST_LAST_CUT: a chunked batch's last chunk is (1 - this) of the others
     bool new_mapped = true;       // KWOK_INGEST_NEW_MAPPED=0: kwok_pod_rec12 create handles copied back, not written in place
+    bool hb_delta = true;       // KWOK_HB_DELTA=0: every tick writes the whole heartbeat stream (A/B, tests)
+    uint32_t hb_gen = 0;        // heartbeat template generation (bumped by every upload of the template or `start`)
     int nt_env = -1;            // KWOK_HB_NT (0 / 1: heartbeat stores plain / non-temporal), else automatic
     int share_env = -1;         // KWOK_TICK_STREAM_SHARE (/1024 of the stream to the streamer blocks), else automatic
     uint32_t tick_tag = 0;      // nonzero id of the last FRONT launch
@@ -622,6 +641,7 @@ int grow_arena(kwok_engine* e, kwok_engine::TickSlot& T) {  // T holds no queued
     if (T.arena) (void)hipFree(T.arena);
     T.arena = nullptr;
     T.arena_cap = 0;
+    T.hb_valid.ok = false;  // a new (possibly poisoned) arena holds no bodies
     if (hipMalloc((void**)&T.arena, need) != hipSuccess) return e->fail(KWOK_ENOMEM, "arena %llu", (unsigned long long)need);
     T.arena_cap = need;
     if (getenv("KWOK_DEBUG_POISON"))  // diagnostics: bytes no kernel writes read as 0xEE, not as stale data
@@ -631,6 +651,7 @@ int grow_arena(kwok_engine* e, kwok_engine::TickSlot& T) {  // T holds no queued
 int alloc_slot(kwok_engine* e, int k) {
     kwok_engine::TickSlot& T = e->slots[k];
     int rc = 0;
+    T.hb_valid.ok = false;
     if ((rc = dalloc(e, &T.hb_nodes, e->NLa)) || (rc = dalloc(e, &T.init_nodes, e->NLa)) ||
         (rc = dalloc(e, &T.init_off, e->NLa)) || (rc = dalloc(e, &T.init_len, e->NLa)) ||
         (rc = dalloc(e, &T.pp_pods, e->PLa)) || (rc = dalloc(e, &T.pp_off, e->PLa)) || (rc = dalloc(e, &T.pp_len, e->PLa)) ||
@@ -1292,6 +1313,7 @@ int kwok_engine_create(const kwok_config* cfg, kwok_engine** out) {
         if (const char* v = getenv("KWOK_TICK_STREAM_DELAY_NS")) S.stream_delay = (uint32_t)std::max(0, atoi(v) / 10);
         if (const char* v = getenv("KWOK_TICK_STREAM_SHARE")) e->share_env = std::min(1024, std::max(0, atoi(v)));
         if (const char* v = getenv("KWOK_HB_NT")) e->nt_env = atoi(v) != 0;
+        if (const char* v = getenv("KWOK_HB_DELTA")) e->hb_delta = atoi(v) != 0;
         if (const char* v = getenv("KWOK_DEBUG_LAYOUT_FAULT_TICK")) e->debug_fault_tick = strtoull(v, nullptr, 10);
         if (const char* v = getenv("KWOK_DEBUG_INGEST_FAIL_CHUNK")) e->debug_fail_chunk = (uint32_t)strtoul(v, nullptr, 10);
         if (const char* v = getenv("KWOK_DEBUG_INGEST_FAIL_APPLY")) e->debug_fail_apply = (uint32_t)strtoul(v, nullptr, 10);
@@ -1402,6 +1424,8 @@ int kwok_engine_create(const kwok_config* cfg, kwok_engine** out) {
         if (r == hipSuccess) r = hipMemcpyAsync((void*)S.hb_kind, kind.data(), HB_MAX_STRIDE, hipMemcpyHostToDevice, e->st);
         if (r == hipSuccess) r = hipStreamSynchronize(e->st);
         if (r != hipSuccess) return bail(e->fail(KWOK_EDEVICE, "template upload: %s", hipGetErrorString(r)));
+        e->hb_gen++;  // (the template and `start` are fixed from here on: nothing else bumps it)
+        for (auto& T : e->slots) T.hb_valid.ok = false;
     }
     {
         const char* sy = getenv("KWOK_SYNC");
@@ -2860,7 +2884,21 @@ int enqueue_tick(kwok_engine* e, int k, bool requeue) {
     auto qstamp = [&](int i) { if (e->iprof) qs[i] = ms_between(q0, clk::now()) * 1e3; };
     hipEvent_t* ev = e->prof ? T.pev : nullptr;
     uint32_t nhb = (uint32_t)e->n_managed;  // = the device's count of managed local node slots
-    if (e->debug_fault_tick && e->front_launches + 1 == e->debug_fault_tick && !requeue) nhb++;  // tests: TICK_ERR_LAYOUT
+    const bool fault_tick = e->debug_fault_tick && e->front_launches + 1 == e->debug_fault_tick && !requeue;
+    if (fault_tick) nhb++;  // tests: TICK_ERR_LAYOUT
+    // the delta stream: only when the slot's record says its arena holds exactly this
+    // tick's layout of bodies.  Multi-rank and heartbeat-once engines always write
+    // everything, and so does a requeued tick (its slot's first launch was skipped)
+    {
+        const kwok_engine::TickSlot::HbValid& V = T.hb_valid;
+        const bool can = e->hb_delta && !S.hb_once && !e->multi && !requeue && !fault_tick && !e->no_stream && V.ok &&
+                         V.arena == T.arena && V.n == nhb && V.stride == e->hb_stride && V.units == S.hb_units &&
+                         V.gen == e->hb_gen;
+        T.hb_prev = can ? V.clock : 0;
+        T.hb_n = nhb;
+        T.hb_record = !requeue && !fault_tick && !e->no_stream && !S.hb_once && !e->multi;
+        T.hb_valid.ok = false;  // the region is being rewritten: known again when this tick retires
+    }
     if (e->hb_pre_dirty) {
         // heartbeat handles are written in node order at per-chain-block bases:
         // managed nodes of the buckets before each block's range (k_hb_pre, from
@@ -2878,6 +2916,8 @@ int enqueue_tick(kwok_engine* e, int k, bool requeue) {
     // no dirty L2 left for the kernel-end write-back)
     const uint64_t hb_bytes = (S.hb_once ? std::min<uint32_t>(nhb, 1u) : nhb) * (uint64_t)e->hb_stride;
     S.hb_nt = e->nt_env >= 0 ? (uint32_t)e->nt_env : (hb_bytes >= (256ull << 20) ? 1u : 0u);
+    // (a delta tick's stores are whole 64-byte lines a quarter of a body apart: plain and
+    // non-temporal stores measured the same, tools/micro/fill_sparse.hip; the rule stays)
     // the streamers' share: with the non-temporal stream the chain blocks finish
     // sooner (1M x 10M: classification 172 -> 122 us) and take more of the tail
     // (tools/share_sweep2.sh: 921 -> 860 /1024, 217 -> 208 us per tick)
@@ -2905,7 +2945,9 @@ int enqueue_tick(kwok_engine* e, int k, bool requeue) {
     // of it would hold up the pool phase, which waits for every dirty block
     S.stream_share = e->n_stream == 0 ? 0u
                      : e->share_env >= 0 ? (uint32_t)e->share_env
-                                         : (hb_bytes < (32ull << 20) || T.split ? 1024u : (S.hb_nt ? 860u : 921u));
+                                         : (hb_bytes < (32ull << 20) || T.split || T.hb_prev ? 1024u
+                                            : S.hb_nt                                        ? 860u
+                                                                                             : 921u);
     S.use_events_only = T.quiet ? 1u : 0u;
     S.foreign = e->foreign_ips ? 1u : 0u;
     int rc = bind_slot(e, k);
@@ -2947,7 +2989,7 @@ int enqueue_tick(kwok_engine* e, int k, bool requeue) {
     } else if (!e->multi) {
         e->sum_valid = false;  // (a k_tick may change pod states)
         launch_tick(S, e->n_stream, now, (uint64_t)e->start, nhb, TICK_FRONT | TICK_BACK | prof, T.tag, T.target, st,
-                    ev ? ev[0] : nullptr, ev ? ev[1] : nullptr);
+                    ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, T.hb_prev);
         HIPCHK(e, hipGetLastError());
         qstamp(2);
     } else {
@@ -3365,6 +3407,15 @@ int retire(kwok_engine* e) {
     e->host_ms[KWOK_H_TOTAL] += ms_between(t1, t3);
     e->host_ticks++;
     e->stats[T.once ? KWOK_STAT_TICKS_ONCE : KWOK_STAT_TICKS_FULL]++;
+    // the slot's heartbeat region now holds this tick's bodies (TickSlot::HbValid); a
+    // tick that was a k_once tick at any point (redone ones included) records nothing
+    if (T.hb_record && !T.once && !T.no_once) {
+        kwok_engine::TickSlot::HbValid& V = T.hb_valid;
+        V.arena = T.arena, V.n = T.hb_n, V.stride = e->hb_stride, V.units = e->S.hb_units, V.gen = e->hb_gen;
+        V.clock = T.now;
+        V.ok = true;
+    }
+    if (T.hb_prev) e->stats[KWOK_STAT_TICKS_HB_DELTA]++;
     if (T.once && T.once_use) e->stats[KWOK_STAT_ONCE_SUMMARY]++;  // (a launch that skipped or was redone read none)
     if (requeue_next) {  // the tick queued behind a redone one skipped on the device
         if (int rc = enqueue_tick(e, next, true)) {

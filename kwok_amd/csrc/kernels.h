@@ -164,8 +164,11 @@ constexpr int TICK_FRONT = 1, TICK_BACK = 2, TICK_PROF = 4, TICK_PRIO = 8, TICK_
                                  // and k_pool_apply_spec applied them if every rank's fit
 // tag: this tick's nonzero id (single-rank dirty records); arrive_target: the
 // arrival count at which every chain block of this FRONT launch has arrived
+// hb_prev: the clock of the bodies the slot's arena provably holds (the stream writes
+// only the 64-byte lines that differ from them), or 0: the whole stream is written
 void launch_tick(const DevState& S, uint32_t n_stream, uint64_t now, uint64_t start, uint32_t n_hb, int phases,
-                 uint32_t tag, uint64_t arrive_target, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+                 uint32_t tag, uint64_t arrive_target, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr,
+                 uint64_t hb_prev = 0);
 // a heartbeat-once tick expected to have nothing to emit (single rank): one
 // wave per bucket counts it; a tick that has work after all sets TickHdr::redo
 // and GridBar::skip (the host runs it again with launch_tick)

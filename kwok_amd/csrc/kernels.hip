@@ -1651,6 +1651,95 @@ __device__ __forceinline__ void build_hb_template(const DevState& S, uint8_t* tm
 }
 
 // ---------------------------------------------------------------------------
+// delta stream: the arena still holds the bodies this slot's previous tick wrote
+// at prev_unix (the host's validity record, engine.cpp: TickSlot::hb_valid), and
+// the two templates differ in a few timestamp characters.  Only the 64-byte
+// lines with a changed byte are stored, whole, from the new template: a group of
+// 4 slots is 4 x hb_units units = hb_units aligned lines whatever the unit
+// count, so the dirty lines are the same in every group.  (16-byte stores cost
+// the part as much as the whole stream, 128-byte lines a third more than 64-byte
+// ones: tools/micro/fill_sparse.hip)
+// ---------------------------------------------------------------------------
+constexpr uint32_t HB_LINE_UNITS = 4;  // 64 bytes
+struct HbDelta {
+    uint32_t n;                                    // units of a group's dirty lines
+    uint8_t mark[HB_MAX_UNITS];                    // units of a body with a byte that differs
+    uint16_t item[HB_GROUP_SLOTS * HB_MAX_UNITS];  // those units, ascending: unit in the group | template unit << 9
+};
+static_assert(HB_GROUP_SLOTS % HB_LINE_UNITS == 0, "a group is whole lines for every unit count");
+static_assert(HB_GROUP_SLOTS * HB_MAX_UNITS <= 512 && HB_MAX_UNITS <= 128, "HbDelta::item packing");
+// groups [g0, g1) of the heartbeat region: tmpl holds the new template (build_hb_template).
+// Every (group, dirty unit) pair is one item of a flat walk, so every lane stores
+// whatever the number of dirty lines; units past n_hb slots are not written.
+__device__ __forceinline__ void hb_fill_delta(const DevState& S, const uint4* tmpl, HbDelta* D, uint64_t prev_unix,
+                                           uint64_t n_hb, uint64_t g0, uint64_t g1) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const uint32_t t = threadIdx.x, U = S.hb_units, GU = HB_GROUP_SLOTS * U;
+    for (uint32_t i = t; i < (uint32_t)HB_MAX_UNITS; i += BLOCK) D->mark[i] = 0;
+    __syncthreads();
+    // the previous template's bytes against the new one's: Now values only (the static
+    // bytes and StartTime are fixed at create); no step of the clock is assumed
+    const Ts prev = format_ts(prev_unix);
+    const uint8_t* tb = reinterpret_cast<const uint8_t*>(tmpl);
+    for (uint32_t i = t; i < 16u * U; i += BLOCK) {
+        const uint8_t k = S.hb_kind[i];
+        if (k < TS_LEN && ts_byte(prev, k) != tb[i]) D->mark[i >> 4] = 1;
+    }
+    __syncthreads();
+    if (t < 64) {  // wave 0 compacts the dirty lines' units of one group
+        uint32_t n = 0;
+        for (uint32_t u0 = 0; u0 < GU; u0 += 64) {
+            const uint32_t u = u0 + t;
+            bool d = false;
+            if (u < GU) {
+                const uint32_t l0 = u - u % HB_LINE_UNITS;  // (GU is a multiple of the line)
+#pragma unroll
+                for (uint32_t x = 0; x < HB_LINE_UNITS; x++) d |= D->mark[(l0 + x) % U] != 0;
+            }
+            const uint64_t m = __ballot(d);
+            if (d) D->item[n + __popcll(m & ((1ull << t) - 1))] = (uint16_t)(u | (u % U) << 9);
+            n += (uint32_t)__popcll(m);
+        }
+        if (t == 0) D->n = n;
+    }
+    __syncthreads();
+    const uint32_t n_e = D->n;
+    if (n_e == 0 || g0 >= g1) return;  // (the same clock twice: nothing to write)
+    const uint64_t units = n_hb * U;
+    u32x4* dst = reinterpret_cast<u32x4*>(S.arena);
+    const uint32_t dg = (uint32_t)BLOCK / n_e, dr = (uint32_t)BLOCK % n_e;
+    uint64_t g = g0 + t / n_e;
+    uint32_t r = t % n_e;
+    const bool nt = S.hb_nt != 0;
+    while (g < g1) {
+        const uint32_t it = D->item[r];
+        const uint64_t i = g * GU + (it & 511u);
+        if (i < units) {
+            const uint4 v = tmpl[it >> 9];
+            const u32x4 x = u32x4{v.x, v.y, v.z, v.w};
+            if (nt) __builtin_nontemporal_store(x, dst + i);
+            else dst[i] = x;
+        }
+        g += dg;
+        r += dr;
+        if (r >= n_e) r -= n_e, g++;
+    }
+}
+// this block's share of the stream (hb_fill_share's split), full or delta
+template <bool GEN>
+__device__ __forceinline__ void hb_write_share(const DevState& S, const uint4* tmpl, HbDelta* D, uint64_t prev_unix,
+                                               uint64_t n_hb, bool streamer, uint32_t idx, uint32_t cnt) {
+    if (prev_unix == 0) {
+        hb_fill_share<GEN>(S, tmpl, n_hb, streamer, idx, cnt);
+        return;
+    }
+    const uint64_t groups = (n_hb + HB_GROUP_SLOTS - 1) / HB_GROUP_SLOTS;
+    const uint64_t cut = groups * S.stream_share / 1024;
+    const uint64_t lo = streamer ? 0 : cut, n = streamer ? cut : groups - cut;
+    hb_fill_delta(S, tmpl, D, prev_unix, n_hb, lo + n * idx / cnt, lo + n * (idx + 1) / cnt);
+}
+
+// ---------------------------------------------------------------------------
 // header / exchange message (FRONT launch, written by the last arriver).  The
 // header is assembled in LDS and stored with one coalesced pass to the device
 // copy and (single rank) the pinned host copy; the host reads it after the
@@ -2012,13 +2101,15 @@ __device__ __forceinline__ void tick_back(const DevState* __restrict__ G, TickLd
 // ---------------------------------------------------------------------------
 template <bool GEN_HB>
 __global__ __launch_bounds__(BLOCK, 2) void k_tick(DevState S, uint64_t now_unix, uint64_t start_unix,
-                                                   uint32_t n_hb, int phases, uint32_t tag, uint64_t arrive_target) {
+                                                   uint32_t n_hb, int phases, uint32_t tag, uint64_t arrive_target,
+                                                   uint64_t prev_unix) {
     const int t = threadIdx.x;
     const uint32_t b = blockIdx.x;
     // reduce_records; then emit_pod_chunk's staging (two k_tick blocks per CU still fit)
     __shared__ uint32_t recs[MAX_CHAIN * REC_PITCH > (BLOCK / 64) * POD_STAGE_WORDS ? MAX_CHAIN * REC_PITCH
                                                                                    : (BLOCK / 64) * POD_STAGE_WORDS];
     __shared__ uint4 hb_tmpl4[HB_MAX_UNITS];
+    __shared__ HbDelta hb_delta;  // prev_unix != 0: the stream's dirty lines (hb_fill_delta)
     __shared__ uint32_t nflags32[NODE_LDS / 4];
     __shared__ uint32_t gpre[MAX_BPB + 1];
     __shared__ uint16_t spec_max[SPEC_LDS];  // the specs' reservations (n_specs <= SPEC_LDS)
@@ -2056,7 +2147,8 @@ __global__ __launch_bounds__(BLOCK, 2) void k_tick(DevState S, uint64_t now_unix
             while (__builtin_amdgcn_s_memrealtime() - t0 < S.stream_delay) __builtin_amdgcn_s_sleep(4);
         }
         if (!(phases & TICK_NOSTREAM))
-            hb_fill_share<GEN_HB>(S, hb_tmpl4, hb_bodies(S, n_hb), true, b - S.n_chain, gridDim.x - S.n_chain);
+            hb_write_share<GEN_HB>(S, hb_tmpl4, &hb_delta, prev_unix, hb_bodies(S, n_hb), true, b - S.n_chain,
+                                   gridDim.x - S.n_chain);
         if ((phases & TICK_PROF) && t == 0) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             atomicMax(&S.bar->stream_end_max, (unsigned long long)__builtin_amdgcn_s_memrealtime());
@@ -2361,7 +2453,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_tick(DevState S, uint64_t now_unix
             TSTAMP(12);
             if (S.stream_share < 1024 && !(phases & TICK_NOSTREAM) && hb_share_any(S, hb_bodies(S, n_hb), b, S.n_chain)) {
                 build_hb_template(S, hb_tmpl, now_unix, start_unix);  // (this block's slice of the stream)
-                hb_fill_share<GEN_HB>(S, hb_tmpl4, hb_bodies(S, n_hb), false, b, S.n_chain);
+                hb_write_share<GEN_HB>(S, hb_tmpl4, &hb_delta, prev_unix, hb_bodies(S, n_hb), false, b, S.n_chain);
             }
             TSTAMP(13);
             if (t < AG_DIRTY && (acc_old >> ACC_SHIFT) == S.n_chain - 1u) {
@@ -2411,7 +2503,7 @@ __global__ __launch_bounds__(BLOCK, 2) void k_tick(DevState S, uint64_t now_unix
             write_hb_handles(S, nflags32, nbase, nn, hb_base);
             if (S.stream_share < 1024 && !(phases & TICK_NOSTREAM) && hb_share_any(S, hb_bodies(S, n_hb), b, S.n_chain)) {
                 build_hb_template(S, hb_tmpl, now_unix, start_unix);
-                hb_fill_share<GEN_HB>(S, hb_tmpl4, hb_bodies(S, n_hb), false, b, S.n_chain);
+                hb_write_share<GEN_HB>(S, hb_tmpl4, &hb_delta, prev_unix, hb_bodies(S, n_hb), false, b, S.n_chain);
             }
             return;  // the BACK launch follows the exchange
         }
@@ -3139,13 +3231,14 @@ void launch_pool_apply(const DevState& S, const ListDesc* ld, int nranks, uint32
 
 
 void launch_tick(const DevState& S, uint32_t n_stream, uint64_t now, uint64_t start, uint32_t n_hb, int phases,
-                 uint32_t tag, uint64_t arrive_target, hipStream_t st, hipEvent_t t0, hipEvent_t t1) {
+                 uint32_t tag, uint64_t arrive_target, hipStream_t st, hipEvent_t t0, hipEvent_t t1, uint64_t hb_prev) {
     const uint32_t grid = S.n_chain + ((phases & TICK_FRONT) ? n_stream : (S.multi ? S.n_pool_extra : 0u));
     auto kern = S.hb_units == (uint32_t)HB_CHUNKS ? k_tick<false> : k_tick<true>;
     if (t0)
         hipExtLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), 0, st, t0, t1, 0, S, now, start, n_hb, phases, tag,
-                              arrive_target);
-    else hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), 0, st, S, now, start, n_hb, phases, tag, arrive_target);
+                              arrive_target, hb_prev);
+    else
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), 0, st, S, now, start, n_hb, phases, tag, arrive_target, hb_prev);
 }
 
 // ---------------------------------------------------------------------------
