@@ -1,4 +1,4 @@
-"""ctypes / numpy mirrors of include/kwok_engine.h (the C-ABI boundary).
+"""ctypes / numpy mirrors of include/kwok_engine.h and include/kwok_watch.h (the C-ABI boundary).
 
 Everything here is layout only; the structs must stay byte-identical to the
 header (tests/test_abi.py checks sizes and offsets against the compiled
@@ -95,6 +95,23 @@ class PodDoc(C.Structure):
                 ("readiness_gates", KwokStr * DOC_MAX_GATES)]
 
 
+# include/kwok_watch.h
+WATCH_NONE, WATCH_ADDED, WATCH_MODIFIED, WATCH_DELETED, WATCH_BOOKMARK, WATCH_ERROR = range(6)
+WATCH_TYPES = {"ADDED": WATCH_ADDED, "MODIFIED": WATCH_MODIFIED, "DELETED": WATCH_DELETED,
+               "BOOKMARK": WATCH_BOOKMARK, "ERROR": WATCH_ERROR}
+FRAME_ESC_UID, FRAME_ESC_RV, FRAME_ESC_NAME, FRAME_ESC_NS = 1, 2, 4, 8
+WATCH_TILE = 16384        # KWOK_WATCH_TILE_BYTES: the bytes one block of the line split covers
+WATCH_SCAN_TILES = 1024   # KWOK_WATCH_SCAN_TILES: the tiles one step of the scan covers
+WATCH_STATS = ("frames", "host_frames", "stream_bytes", "framed_ingests")  # KWOK_WATCH_STAT_* order
+
+
+class WatchFrame(C.Structure):
+    """kwok_watch_frame: one line of a watch stream (offsets into the stream)"""
+    _fields_ = [("line_off", C.c_uint32), ("doc_off", C.c_uint32), ("doc_len", C.c_uint32),
+                ("type", C.c_uint8), ("flags", C.c_uint8), ("status", C.c_int8), ("reserved0", C.c_uint8),
+                ("uid", KwokStr), ("resource_version", KwokStr), ("name", KwokStr), ("namespace_", KwokStr)]
+
+
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 
@@ -153,6 +170,7 @@ NODE_EVENT_DTYPE = _np_dtype(NodeEvent)
 POD_EVENT_DTYPE = _np_dtype(PodEvent)
 POD_REC_DTYPE = _np_dtype(PodRec)
 POD_REC12_DTYPE = _np_dtype(PodRec12)
+WATCH_FRAME_DTYPE = _np_dtype(WatchFrame)
 
 
 def ip4(s: str) -> int:

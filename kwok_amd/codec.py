@@ -31,6 +31,25 @@ def selector_matches(selector: str, labels: dict | None) -> bool:
     return bool(out.value)
 
 
+def frame_watch(data, cap=None):
+    """kwok_frame_watch, the host framer (include/kwok_watch.h): raw watch bytes ->
+    (frames (WATCH_FRAME_DTYPE), consumed).  cap: the frames array's size (default: the
+    line count); KwokError(EINVAL) when it is smaller, with .n_frames set."""
+    import numpy as np
+    lib = load_engine_lib()
+    data = bytes(data)
+    if cap is None:
+        cap = data.count(b"\n")
+    frames = np.zeros(max(cap, 1), abi.WATCH_FRAME_DTYPE)
+    nf, used = C.c_size_t(), C.c_size_t()
+    rc = lib.kwok_frame_watch(data or b"\0", len(data), frames.ctypes.data, cap, C.byref(nf), C.byref(used))
+    if rc < 0:
+        err = KwokError(rc, "frame_watch: %s" % lib.kwok_codec_last_error().decode())
+        err.n_frames = nf.value
+        raise err
+    return frames[:nf.value], used.value
+
+
 class Batch:
     """Decoded records of one ingest batch plus their shared arena."""
 

@@ -52,6 +52,14 @@ Per tick (step):
 
 The backend is the HIP engine; tests may pass another implementation of the
 same ABI (the CPU oracle) as the checker.
+
+feed_watch is the same controller fed with the raw bytes of the watch responses
+(a rest.Request.Stream read loop instead of the typed watcher): step 1-3 then
+run on frames (include/kwok_watch.h) - the stream of each kind is framed on the
+GPU (kwok_frame_watch_gpu), echoes are dropped by the frames' uid and
+resourceVersion, and the kept frames are ingested from the resident stream
+(kwok_ingest_nodes_framed / kwok_ingest_pods_framed, pods in the same runs): no
+object is decoded or serialised on the host.
 """
 from __future__ import annotations
 
@@ -268,6 +276,10 @@ class Stats:
     pod_docs_host: int = 0  # pod documents the GPU codec left to the host codec
     node_docs_host: int = 0  # node documents the GPU codec left to the host codec
     pod_runs: int = 0
+    watch_frames: int = 0       # feed_watch: lines framed
+    watch_host_frames: int = 0  # ... of them by the host framer (an escaped type or routed key)
+    watch_bad_frames: int = 0   # frames whose status is not OK (malformed lines, unknown types): skipped
+    watch_skipped: int = 0      # BOOKMARK / ERROR frames: skipped
     bodies: int = 0
     rejected: list = field(default_factory=list)
 
@@ -324,6 +336,8 @@ class Controller:
         self.spec_ids = {}
         self.finalizer = None
         self.reenter = []     # objects of pod patches without a podIP (step 6)
+        self.raw = {True: bytearray(), False: bytearray()}  # feed_watch: raw watch bytes per kind (nodes: True)
+        self.fed = set()      # the kinds fed raw bytes since the last step
 
     def close(self):
         self.eng.close()
@@ -336,7 +350,20 @@ class Controller:
                  label_selector=self.conf.manage_nodes_with_label_selector)
         cs.watch("pods", lambda typ, obj: self.on_event(False, typ, obj), field_selector="spec.nodeName!=")
 
+    def feed_watch(self, nodes: bool, data: bytes):
+        """raw bytes of the node (nodes=True) or pod watch response, cut anywhere: they
+        are framed and ingested at the next step; an unterminated last line waits
+        for its rest"""
+        if not hasattr(self.eng, "frame_watch"):
+            raise ValueError("feed_watch needs the engine backend (kwok_frame_watch_gpu)")
+        if self.nodes if nodes else self.pods:
+            raise ValueError("feed_watch after on_event for the same kind within one step")
+        self.fed.add(bool(nodes))
+        self.raw[bool(nodes)] += data
+
     def on_event(self, nodes: bool, typ: str, obj: dict):
+        if bool(nodes) in self.fed:
+            raise ValueError("on_event after feed_watch for the same kind within one step")
         if typ not in ("ADDED", "MODIFIED", "DELETED"):
             return
         md = _meta(obj)
@@ -361,10 +388,15 @@ class Controller:
     def step(self, now: int) -> int:
         nw, pw = self.nodes, self.pods
         self.nodes, self.pods, self.queued = [], [], set()
+        fed, self.fed = self.fed, set()
         nb = self._encode(nw)
         pb = self._encode(pw)
         self._flush_nodes(nb)
+        if True in fed:
+            self._flush_watch(True)
         self._flush_pods(pb)
+        if False in fed:
+            self._flush_watch(False)
         if self.conf.enable_cni:
             self._setup_cni()
         n = self._tick(now)
@@ -536,6 +568,94 @@ class Controller:
                 h = int(hs[k])
                 self.pod_uid[h] = w.uid
                 self.pod_ref[h] = (md.get("namespace", ""), md.get("name", ""))
+
+    def _flush_watch(self, nodes):
+        """step 1-3 over the raw bytes of one kind's watch: framed on the GPU, echoes
+        dropped by the frames' (uid, resourceVersion) under _encode's rule, the kept
+        frames ingested from the resident stream; names for the patches from the
+        frames' spans.  The unconsumed tail stays buffered."""
+        stream = bytes(self.raw[nodes])
+        frames, used, n_host, sid = self.eng.frame_watch(stream)
+        self.raw[nodes] = bytearray(stream[used:])
+        self.stats.watch_frames += len(frames)
+        self.stats.watch_host_frames += n_host
+
+        def text(f, key, bit):
+            raw = stream[int(f[key]["off"]):int(f[key]["off"]) + int(f[key]["len"])]
+            return json.loads(b'"' + raw + b'"') if f["flags"] & bit else raw.decode()
+
+        keep, uids, deleted, seen = [], [], [], set()
+        for i, f in enumerate(frames):
+            if f["status"] != abi.OK:
+                self.stats.watch_bad_frames += 1
+                continue
+            if f["type"] in (abi.WATCH_BOOKMARK, abi.WATCH_ERROR):
+                self.stats.watch_skipped += 1
+                continue
+            if f["type"] == abi.WATCH_NONE:
+                continue
+            uid, rv = text(f, "uid", abi.FRAME_ESC_UID), text(f, "resource_version", abi.FRAME_ESC_RV)
+            dl = f["type"] == abi.WATCH_DELETED
+            if self.suppress and not dl and self.echo.is_echo(uid, rv) and uid not in seen:
+                self.stats.echoes_at_flush += 1
+                continue
+            seen.add(uid)
+            if dl:
+                self.echo.forget(uid)
+            keep.append(i)
+            uids.append(uid)
+            deleted.append(dl)
+        if not keep:
+            return
+        keep = np.array(keep, np.uint32)
+        name = lambda i: text(frames[i], "name", abi.FRAME_ESC_NAME)  # noqa: E731
+        ns = lambda i: text(frames[i], "namespace_", abi.FRAME_ESC_NS)  # noqa: E731
+        if nodes:
+            hs, st, nh = self.eng.ingest_nodes_framed(self.codec, sid, keep)
+            self.stats.node_docs_host += nh
+            self.stats.node_records += int(np.isin(st, (abi.EDOMAIN, abi.EINVAL), invert=True).sum())
+            for k, i in enumerate(keep):
+                if st[k] != abi.OK:
+                    if st[k] in (abi.EDOMAIN, abi.EINVAL):
+                        self.stats.rejected.append(("node", name(i), int(st[k])))
+                    continue
+                if deleted[k]:
+                    self.node_name.pop(int(hs[k]), None)
+                    self.node_handle.pop(name(i), None)
+                else:
+                    self.node_name[int(hs[k])] = name(i)
+                    self.node_handle[name(i)] = int(hs[k])
+            return
+        n_host = [0]
+
+        def send(idx, ops, hv):
+            h1, s1, _rel, nh = self.eng.ingest_pods_framed(self.codec, sid, keep[idx], hv.astype(np.int32))
+            n_host[0] += nh
+            return h1, s1
+
+        hs, st, runs = ingest_pod_runs(self.eng, self.pod_by_uid, np.empty(len(keep)), uids, deleted, None, sender=send)
+        self.stats.pod_records += int((st != NOT_SENT).sum())
+        self.stats.pod_runs += runs
+        self.stats.pod_docs_host += n_host[0]
+        for k, i in enumerate(keep):
+            if st[k] not in (abi.OK, NOT_SENT):
+                self.stats.rejected.append(("pod", name(i), int(st[k])))
+                continue
+            if deleted[k]:
+                # EnableCNI: cni.Remove for a pod on a managed node, before its handle's bookkeeping
+                # (_flush_pods_gpu's order); spec.nodeName is not in the frame: the document is read
+                if self.conf.enable_cni and self.conf.cni:
+                    f = frames[i]
+                    obj = json.loads(stream[int(f["doc_off"]):int(f["doc_off"]) + int(f["doc_len"])])
+                    if self.has((obj.get("spec") or {}).get("nodeName", "")):
+                        self.conf.cni.remove(uids[k], name(i), ns(i))
+                if st[k] == abi.OK:
+                    self.pod_uid.pop(int(hs[k]), None)
+                    self.pod_ref.pop(int(hs[k]), None)
+            else:
+                h = int(hs[k])
+                self.pod_uid[h] = uids[k]
+                self.pod_ref[h] = (ns(i), name(i))
 
     def _setup_cni(self):
         hs = self.eng.cni_pending()

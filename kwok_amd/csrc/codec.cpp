@@ -852,3 +852,78 @@ int kwok_decode_pods(const kwok_codec* c, char* arena, size_t arena_len, const u
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- watch frames
+// kwok_frame_watch (kwok_watch.h): the host framer, the yardstick of the device
+// framer (json.hip k_frame_parse) and the decider of the lines that one lists.
+// One line = one watch.Event as the apiserver writes it; client-go decodes it
+// into a typed object and switches on event.Type (pod_controller.go:272-343,
+// node_controller.go:225-279) - here only the type, the object's span and the
+// four metadata strings a controller routes on are kept.
+void kwok::frame_line(const char* stream, uint32_t lo, uint32_t hi, kwok_watch_frame* f) {
+    memset(f, 0, sizeof *f);
+    f->line_off = lo;
+    f->type = KWOK_WATCH_NONE;
+    f->status = KWOK_OK;
+    uint32_t k = lo;
+    while (k < hi && (stream[k] == ' ' || stream[k] == '\t' || stream[k] == '\r' || stream[k] == '\n')) k++;
+    if (k == hi) return;  // a blank line
+    f->status = KWOK_EINVAL;
+    std::deque<std::string> store;
+    JV root;
+    Parser ps(stream, lo, hi - lo, &store);
+    if (!ps.document(root) || root.t != JV::OBJ) return;
+    const JV* ty = root.get("type");
+    uint8_t type = KWOK_WATCH_NONE;
+    if (ty && ty->t == JV::STR) {
+        static const char* words[] = {"ADDED", "MODIFIED", "DELETED", "BOOKMARK", "ERROR"};
+        for (int w = 0; w < 5; w++)
+            if (ty->s == words[w]) type = (uint8_t)(KWOK_WATCH_ADDED + w);
+    }
+    if (type == KWOK_WATCH_NONE) return;  // client-go: "got invalid watch event type"
+    const JV* ob = root.get("object");
+    if (!ob || ob->t != JV::OBJ) return;
+    f->status = KWOK_OK;
+    f->type = type;
+    f->doc_off = ob->off;
+    f->doc_len = ob->len;
+    const JV* md = ob->get("metadata");
+    if (!md || md->t != JV::OBJ) return;
+    const char* keys[4] = {"uid", "resourceVersion", "name", "namespace"};
+    kwok_str* outs[4] = {&f->uid, &f->resource_version, &f->name, &f->namespace_};
+    for (int q = 0; q < 4; q++) {
+        const JV* v = md->get(keys[q]);
+        if (!v || v->t != JV::STR) continue;  // a non-string value: an empty span
+        if (v->len) *outs[q] = kwok_str{v->off, v->len};
+        if (v->escaped) f->flags |= (uint8_t)(1u << q);  // KWOK_FRAME_ESC_*: the span is the raw text
+    }
+}
+
+extern "C" int kwok_frame_watch(const char* stream, size_t len, kwok_watch_frame* frames, size_t cap, size_t* n_frames,
+                                size_t* consumed) {
+    static_assert(sizeof(kwok_watch_frame) == 48, "kwok_watch_frame is 48 bytes");
+    static_assert(KWOK_FRAME_ESC_UID == 1 && KWOK_FRAME_ESC_RV == 2 && KWOK_FRAME_ESC_NAME == 4 && KWOK_FRAME_ESC_NS == 8,
+                  "flag bits in key order");
+    if (n_frames) *n_frames = 0;
+    if (consumed) *consumed = 0;
+    if (!n_frames || !consumed || len > 0xFFFFFFF0ull || (len && !stream) || (cap && !frames))
+        return fail(KWOK_EINVAL, "kwok_frame_watch: null argument or stream > 4 GiB");
+    size_t n = 0, last = 0;
+    for (const char* p = stream; len && (p = (const char*)memchr(p, '\n', (size_t)(stream + len - p))); p++) {
+        n++;
+        last = (size_t)(p - stream) + 1;
+    }
+    *n_frames = n;
+    *consumed = last;
+    if (n > cap) return fail(KWOK_EINVAL, "kwok_frame_watch: cap smaller than the line count");
+    int bad = 0;
+    uint32_t lo = 0;
+    for (size_t i = 0; i < n; i++) {
+        const char* nl = (const char*)memchr(stream + lo, '\n', len - lo);
+        const uint32_t hi = (uint32_t)(nl - stream);
+        kwok::frame_line(stream, lo, hi, &frames[i]);
+        bad += frames[i].status != KWOK_OK;
+        lo = hi + 1;
+    }
+    return bad;
+}

@@ -242,7 +242,31 @@ struct kwok_engine {
         hipEvent_t idone = nullptr;  // a pod batch's last operation (the host spins on it: KWOK_SYNC)
         hipEvent_t rdone = nullptr;  // the results stream's work of a batch (kwok_pod_rec12: before the summaries)
         size_t chunk = 1048576;
+        // the framed ingests (kwok_watch.h): the records' strings are in the resident watch
+        // stream, not in d_arena (null: d_arena)
+        const uint8_t* arena_src = nullptr;
     } ing;
+
+    // ---- the watch stream framer (json.hip k_frame_*): the resident stream, its
+    // frames on the device and on the host, the caller's bytes (listed lines and
+    // documents are completed from them) ----
+    struct Watch {
+        uint8_t* stream = nullptr;     // [cap] the stream, padded to whole 16-byte windows
+        size_t cap = 0;
+        uint64_t len = 0;
+        const char* host = nullptr;    // the caller's buffer (valid until the next framing call)
+        uint32_t *tile_cnt = nullptr, *tile_base = nullptr;
+        size_t tile_cap = 0;
+        uint32_t* ends = nullptr;      // [fcap] newline offsets
+        kwok_watch_frame* frames = nullptr;  // [fcap]
+        uint32_t* host_list = nullptr; // [fcap]
+        size_t fcap = 0;
+        uint32_t* counts = nullptr;    // device [2]: newlines, listed lines
+        uint32_t* counts_h = nullptr;  // pinned [2]
+        std::vector<kwok_watch_frame> frames_h;
+        uint64_t id = 0, next_id = 1;  // id 0: no stream resident
+        uint64_t stats[KWOK_WATCH_STAT_COUNT] = {};
+    } watch;
 
     // ---- the pod codec on the GPU (json.hip): per-document buffers, the codec's
     // selectors, the spec table (kwok_spec_key -> spec id) ----
@@ -903,7 +927,7 @@ IngestBatch ingest_batch(kwok_engine* e, uint32_t n, size_t arena_len) {
     I.ev = G.d_ev;
     I.n = n;
     I.n_specs = (uint32_t)e->specs_h.size();
-    I.arena = G.d_arena;
+    I.arena = G.arena_src ? G.arena_src : G.d_arena;
     I.arena_len = arena_len;
     I.rec = G.rec;
     I.keys = G.keys;
@@ -1155,6 +1179,13 @@ void kwok_engine_destroy(kwok_engine* e) {
             if (p) (void)hipFree(p);
         if (J.cfg_h) (void)hipHostFree(J.cfg_h);
         if (J.n_host_h) (void)hipHostFree(J.n_host_h);
+    }
+    {
+        auto& Wt = e->watch;
+        void* wp[] = {Wt.stream, Wt.tile_cnt, Wt.tile_base, Wt.ends, Wt.frames, Wt.host_list, Wt.counts};
+        for (void* p : wp)
+            if (p) (void)hipFree(p);
+        if (Wt.counts_h) (void)hipHostFree(Wt.counts_h);
     }
     if (e->h_xall) (void)hipHostFree(e->h_xall);
     if (e->pinned) (void)hipHostFree(e->pinned);
@@ -1726,7 +1757,7 @@ int ingest_nodes_impl(kwok_engine* e, const kwok_node_event* ev, size_t n, const
     N.ev = static_cast<const kwok_node_event*>(zev ? zev : (const void*)G.d_nev);
     N.n = (uint32_t)n;
     N.host_all = e->custom_node ? 1u : 0u;
-    N.arena = zar ? static_cast<const uint8_t*>(zar) : G.d_arena;
+    N.arena = zar ? static_cast<const uint8_t*>(zar) : G.arena_src ? G.arena_src : G.d_arena;
     N.arena_len = arena_len;
     N.empty_blob = e->empty_blob;
     N.rec = G.nrec;
@@ -1903,7 +1934,7 @@ int ingest_pods_impl(kwok_engine* e, const void* recs, int packed, size_t n, con
     if (!n) return tick_now >= 0 ? tick_submit_impl(e, tick_now) : 0;
     e->pod_records_since_tick += n;
     const auto t0 = clk::now();
-    int rc = ingest_reserve(e, n, arena_len);
+    int rc = ingest_reserve(e, n, e->ing.arena_src ? 0 : arena_len);  // (a framed batch: its strings are resident)
     if (rc) return rc;
     auto& G = e->ing;
     hipStream_t st = e->st, ps = G.pst;
@@ -2289,11 +2320,14 @@ int json_reserve(kwok_engine* e, size_t n) {
 // buffers, k_json_pods writes the records there (ingest form when op != null);
 // returns the number of documents listed for the host (JSON_HOST / JSON_SPEC)
 int json_decode(kwok_engine* e, const kwok_codec* c, const char* arena, size_t arena_len, const uint64_t* doc_off,
-                const uint32_t* doc_len, size_t n, const uint8_t* op, const int32_t* handle, uint32_t* n_host) {
+                const uint32_t* doc_len, size_t n, const uint8_t* op, const int32_t* handle, uint32_t* n_host,
+                const uint8_t* resident = nullptr) {
+    // resident: the documents are on the device already, at this address (the watch
+    // stream, kwok_ingest_pods_framed): nothing is copied, one decode launch
     auto& G = e->ing;
     auto& J = e->json;
     hipStream_t st = e->st;
-    int rc = ingest_reserve(e, n, arena_len + 16);  // (the scanner reads whole 16-byte windows)
+    int rc = ingest_reserve(e, n, resident ? 0 : arena_len + 16);  // (the scanner reads whole 16-byte windows)
     if (rc) return rc;
     if ((rc = json_reserve(e, n))) return rc;
     // selectors beyond the device's tables (JSEL_*): every document is decoded by the
@@ -2318,7 +2352,7 @@ int json_decode(kwok_engine* e, const kwok_codec* c, const char* arena, size_t a
     // Otherwise one copy, then one decode.
     bool sorted = true;
     for (size_t i = 1; i < n && sorted; i++) sorted = doc_off[i] >= doc_off[i - 1] + doc_len[i - 1];
-    const uint32_t K = sorted && arena_len > (64u << 20) ? (uint32_t)std::min<size_t>(8, n / 4096 + 1) : 1u;
+    const uint32_t K = !resident && sorted && arena_len > (64u << 20) ? (uint32_t)std::min<size_t>(8, n / 4096 + 1) : 1u;
     hipStream_t ps = G.pst;
     HIPCHK(e, hipEventRecord(G.go, st));  // the copies start after the engine stream's earlier work
     HIPCHK(e, hipStreamWaitEvent(ps, G.go, 0));
@@ -2328,14 +2362,14 @@ int json_decode(kwok_engine* e, const kwok_codec* c, const char* arena, size_t a
     for (uint32_t k = 0; k < K; k++) {
         const size_t d0 = n * k / K, d1 = n * (k + 1) / K;
         const uint64_t hi = k + 1 == K ? arena_len : std::min<uint64_t>(arena_len, doc_off[d1 - 1] + doc_len[d1 - 1]);
-        if (hi > copied) {
+        if (hi > copied && !resident) {
             HIPCHK(e, hipMemcpyAsync(G.d_arena + copied, arena + copied, hi - copied, hipMemcpyHostToDevice, ps));
             copied = hi;
         }
         HIPCHK(e, hipEventRecord(G.prepped[k & 1], ps));
         HIPCHK(e, hipStreamWaitEvent(st, G.prepped[k & 1], 0));
         JsonPodArgs A{};
-        A.arena = G.d_arena;
+        A.arena = resident ? resident : G.d_arena;
         A.arena_len = arena_len;
         A.doc_off = J.off + d0;
         A.doc_len = J.len + d0;
@@ -2483,9 +2517,10 @@ namespace {
 // KWOK_OP_UPSERT when op is null; 0xFF for a document not decided there), the
 // decode statuses into dstat, the number listed for the host (json.host_list) in *nh
 int json_nodes_decode(kwok_engine* e, const kwok_codec* c, const char* arena, size_t arena_len, const uint64_t* doc_off,
-                      const uint32_t* doc_len, const uint8_t* op, size_t n, std::vector<int32_t>& dstat, uint32_t* nh) {
+                      const uint32_t* doc_len, const uint8_t* op, size_t n, std::vector<int32_t>& dstat, uint32_t* nh,
+                      const uint8_t* resident = nullptr) {  // (resident: as json_decode's)
     const auto t0 = clk::now();
-    int rc = node_reserve(e, n, arena_len + 16);  // (the scanner reads whole 16-byte windows)
+    int rc = node_reserve(e, n, resident ? 0 : arena_len + 16);  // (the scanner reads whole 16-byte windows)
     if (rc) return rc;
     if ((rc = json_reserve(e, n))) return rc;
     auto& G = e->ing;
@@ -2513,21 +2548,21 @@ int json_nodes_decode(kwok_engine* e, const kwok_codec* c, const char* arena, si
     // the arena in pieces on the prep stream, each piece's documents decoded as it lands
     bool sorted = true;
     for (size_t i = 1; i < n && sorted; i++) sorted = doc_off[i] >= doc_off[i - 1] + doc_len[i - 1];
-    const uint32_t K = sorted && arena_len > (64u << 20) ? (uint32_t)std::min<size_t>(8, n / 4096 + 1) : 1u;
+    const uint32_t K = !resident && sorted && arena_len > (64u << 20) ? (uint32_t)std::min<size_t>(8, n / 4096 + 1) : 1u;
     HIPCHK(e, hipEventRecord(G.go, st));
     HIPCHK(e, hipStreamWaitEvent(ps, G.go, 0));
     uint64_t copied = 0;
     for (uint32_t k = 0; k < K; k++) {
         const size_t d0 = n * k / K, d1 = n * (k + 1) / K;
         const uint64_t hi = k + 1 == K ? arena_len : std::min<uint64_t>(arena_len, doc_off[d1 - 1] + doc_len[d1 - 1]);
-        if (hi > copied) {
+        if (hi > copied && !resident) {
             HIPCHK(e, hipMemcpyAsync(G.d_arena + copied, arena + copied, hi - copied, hipMemcpyHostToDevice, ps));
             copied = hi;
         }
         HIPCHK(e, hipEventRecord(G.prepped[k & 1], ps));
         HIPCHK(e, hipStreamWaitEvent(st, G.prepped[k & 1], 0));
         JsonNodeArgs A{};
-        A.arena = G.d_arena;
+        A.arena = resident ? resident : G.d_arena;
         A.arena_len = arena_len;
         A.doc_off = J.off + d0;
         A.doc_len = J.len + d0;
@@ -2571,12 +2606,25 @@ int json_nodes_listed(kwok_engine* e, uint32_t nh, std::vector<uint32_t>& list) 
 // capacity blob, whose canonical form is the host's, or an escaped routed
 // string), then kwok_ingest_nodes' GPU event switch over the records, which
 // stay on the device.
+namespace {
+int ingest_nodes_json_impl(kwok_engine* e, const kwok_codec* c, const char* arena, size_t arena_len,
+                           const uint64_t* doc_off, const uint32_t* doc_len, const uint8_t* op, size_t n,
+                           int32_t* out_handles, int32_t* out_status, size_t* n_host, const uint8_t* resident);
+}
 int kwok_ingest_nodes_json(kwok_engine* e, const kwok_codec* c, const char* arena, size_t arena_len,
                            const uint64_t* doc_off, const uint32_t* doc_len, const uint8_t* op, size_t n,
                            int32_t* out_handles, int32_t* out_status, size_t* n_host) {
     if (!e || !c || (n && (!doc_off || !doc_len || !op)) || (arena_len && !arena) || n > 0x7FFFFFF0ull ||
         arena_len > 0xFFFFFFF0ull)
         return KWOK_EINVAL;
+    return ingest_nodes_json_impl(e, c, arena, arena_len, doc_off, doc_len, op, n, out_handles, out_status, n_host, nullptr);
+}
+namespace {
+// resident: the documents are in the watch stream on the device (kwok_ingest_nodes_framed);
+// arena is then the caller's copy of it, read for the documents the host completes
+int ingest_nodes_json_impl(kwok_engine* e, const kwok_codec* c, const char* arena, size_t arena_len,
+                           const uint64_t* doc_off, const uint32_t* doc_len, const uint8_t* op, size_t n,
+                           int32_t* out_handles, int32_t* out_status, size_t* n_host, const uint8_t* resident) {
     if (e->poisoned) return poisoned(e);
     drain(e);
     if (e->poisoned) return poisoned(e);
@@ -2588,7 +2636,7 @@ int kwok_ingest_nodes_json(kwok_engine* e, const kwok_codec* c, const char* aren
     const auto t0 = clk::now();
     std::vector<int32_t> dstat;
     uint32_t nh = 0;
-    int rc = json_nodes_decode(e, c, arena, arena_len, doc_off, doc_len, op, n, dstat, &nh);
+    int rc = json_nodes_decode(e, c, arena, arena_len, doc_off, doc_len, op, n, dstat, &nh, resident);
     if (rc) return rc;
     auto& G = e->ing;
     auto& J = e->json;
@@ -2647,6 +2695,7 @@ int kwok_ingest_nodes_json(kwok_engine* e, const kwok_codec* c, const char* aren
         }
     return rc;
 }
+}  // namespace
 
 // kwok_decode_nodes_gpu: the decode alone (tests): the records kwok_decode_nodes
 // would write, the listed documents decoded by the host codec in place (it
@@ -2742,6 +2791,222 @@ int kwok_ingest_pods_json(kwok_engine* e, const kwok_codec* c, const char* arena
     // the event switch over the decoded records, which stayed on the device
     return ingest_pods_impl(e, e->ing.d_ev, 0, n, nullptr, arena_len, out_handles, out_status, nullptr, out_released,
                             true);
+}
+
+// ---- watch streams (kwok_watch.h): framed on the device, ingested in place -----
+namespace {
+static int watch_reserve(kwok_engine* e, size_t len) {
+    auto& Wt = e->watch;
+    if (!Wt.counts) {
+        if (int rc = dalloc(e, &Wt.counts, 2)) return rc;
+        if (hipHostMalloc((void**)&Wt.counts_h, 2 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
+            return e->fail(KWOK_ENOMEM, "watch framer staging");
+    }
+    const size_t need = ((len + 15) & ~(size_t)15) + 16;  // (the readers take whole 16-byte windows)
+    if (need > Wt.cap) {
+        if (Wt.stream) (void)hipFree(Wt.stream);
+        Wt.stream = nullptr, Wt.cap = 0;
+        const size_t cap = std::max<size_t>(need + need / 4, 1 << 16);
+        if (int rc = dalloc(e, &Wt.stream, cap)) return rc;
+        Wt.cap = cap;
+    }
+    const size_t tiles = (len + KWOK_WATCH_TILE_BYTES - 1) / KWOK_WATCH_TILE_BYTES;
+    if (tiles > Wt.tile_cap) {
+        if (Wt.tile_cnt) (void)hipFree(Wt.tile_cnt);
+        if (Wt.tile_base) (void)hipFree(Wt.tile_base);
+        Wt.tile_cnt = Wt.tile_base = nullptr, Wt.tile_cap = 0;
+        const size_t cap = std::max<size_t>(tiles + tiles / 4, 1024);
+        int rc = 0;
+        if ((rc = dalloc(e, &Wt.tile_cnt, cap)) || (rc = dalloc(e, &Wt.tile_base, cap))) return rc;
+        Wt.tile_cap = cap;
+    }
+    return KWOK_OK;
+}
+static int watch_reserve_frames(kwok_engine* e, size_t n) {
+    auto& Wt = e->watch;
+    if (n <= Wt.fcap) return KWOK_OK;
+    void* ptrs[] = {Wt.ends, Wt.frames, Wt.host_list};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+    Wt.ends = nullptr, Wt.frames = nullptr, Wt.host_list = nullptr, Wt.fcap = 0;
+    const size_t cap = std::max<size_t>(n + n / 4, 4096);
+    int rc = 0;
+    if ((rc = dalloc(e, &Wt.ends, cap)) || (rc = dalloc(e, &Wt.frames, cap)) || (rc = dalloc(e, &Wt.host_list, cap))) return rc;
+    Wt.fcap = cap;
+    return KWOK_OK;
+}
+// the records of a framed batch from the host's copy of the frames: the object's
+// span and the op of the frame type; a record that names no ingestible frame gets
+// a span outside the stream, which the decode kernels answer with KWOK_EINVAL
+// (k_json_pods / k_json_nodes: "a span outside the arena") and nothing applies
+static int framed_records(kwok_engine* e, uint64_t stream_id, const uint32_t* frame_idx, size_t n, std::vector<uint64_t>& off,
+                   std::vector<uint32_t>& len, std::vector<uint8_t>& op) {
+    auto& Wt = e->watch;
+    if (!stream_id || stream_id != Wt.id) return e->fail(KWOK_EINVAL, "stream_id is not the resident watch stream");
+    off.resize(n), len.resize(n), op.resize(n);
+    for (size_t i = 0; i < n; i++) {
+        const kwok_watch_frame* f = frame_idx[i] < Wt.frames_h.size() ? &Wt.frames_h[frame_idx[i]] : nullptr;
+        const bool ok = f && f->status == KWOK_OK &&
+                        (f->type == KWOK_WATCH_ADDED || f->type == KWOK_WATCH_MODIFIED || f->type == KWOK_WATCH_DELETED);
+        off[i] = ok ? f->doc_off : ~0ull;
+        len[i] = ok ? f->doc_len : 0u;
+        op[i] = ok && f->type == KWOK_WATCH_DELETED ? KWOK_OP_DELETE : KWOK_OP_UPSERT;
+    }
+    return KWOK_OK;
+}
+struct ArenaSrc {  // the ingest kernels read the batch's strings from the resident stream
+    kwok_engine* e;
+    ArenaSrc(kwok_engine* e_, const uint8_t* p) : e(e_) { e->ing.arena_src = p; }
+    ~ArenaSrc() { e->ing.arena_src = nullptr; }
+};
+}  // namespace
+
+int kwok_frame_watch_gpu(kwok_engine* e, const char* stream, size_t len, kwok_watch_frame* frames, size_t cap,
+                         size_t* n_frames, size_t* consumed, size_t* n_host, uint64_t* stream_id) {
+    if (n_frames) *n_frames = 0;
+    if (consumed) *consumed = 0;
+    if (n_host) *n_host = 0;
+    if (stream_id) *stream_id = 0;
+    if (!e || !n_frames || !consumed || !stream_id || len > 0xFFFFFFF0ull || (len && !stream) || (cap && !frames))
+        return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    auto& Wt = e->watch;
+    hipStream_t st = e->st;
+    Wt.id = 0;  // (a failed call leaves no stream resident)
+    Wt.frames_h.clear();
+    int rc = watch_reserve(e, len);
+    if (rc) return rc;
+    const uint32_t tiles = (uint32_t)((len + KWOK_WATCH_TILE_BYTES - 1) / KWOK_WATCH_TILE_BYTES);
+    const size_t padded = ((len + 15) & ~(size_t)15) + 16;
+    // KWOK_INGEST_PROF: device-side stamps - upload | count + scan | emit | parse
+    hipEvent_t pe[5] = {};
+    const auto t0 = clk::now();
+    if (e->iprof)
+        for (auto& x : pe) (void)hipEventCreate(&x);
+    auto stamp = [&](int k) {
+        if (pe[k]) (void)hipEventRecord(pe[k], st);
+    };
+    struct PeFree {
+        hipEvent_t* p;
+        ~PeFree() {
+            for (int k = 0; k < 5; k++)
+                if (p[k]) (void)hipEventDestroy(p[k]);
+        }
+    } pe_free{pe};
+    stamp(0);
+    if (len) HIPCHK(e, hipMemcpyAsync(Wt.stream, stream, len, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemsetAsync(Wt.stream + len, 0, padded - len, st));
+    Wt.stats[KWOK_WATCH_STAT_BYTES] += len;
+    stamp(1);
+    launch_frame_count(Wt.stream, len, tiles, Wt.tile_cnt, st);
+    launch_frame_scan(Wt.tile_cnt, tiles, Wt.tile_base, Wt.counts, st);
+    HIPCHK(e, hipGetLastError());
+    stamp(2);
+    HIPCHK(e, hipMemcpyAsync(Wt.counts_h, Wt.counts, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    const uint32_t n = Wt.counts_h[0];
+    *n_frames = n;
+    if (n > cap) return e->fail(KWOK_EINVAL, "kwok_frame_watch_gpu: cap smaller than the line count (%u)", n);
+    if (!n) {  // (no newline: nothing consumed, no frame - but the call succeeded: an empty stream is resident)
+        Wt.len = len, Wt.host = stream;
+        *stream_id = Wt.id = Wt.next_id++;
+        return 0;
+    }
+    if ((rc = watch_reserve_frames(e, n))) return rc;
+    const bool prof = pe[0] != nullptr;
+    if (prof) (void)hipEventRecord(pe[0], st);  // (re-used: the emit's start, after the host's wait for the count)
+    launch_frame_emit(Wt.stream, len, tiles, Wt.tile_base, Wt.ends, n, st);
+    stamp(3);
+    HIPCHK(e, hipMemsetAsync(Wt.counts + 1, 0, 4, st));
+    launch_frame_parse(Wt.stream, Wt.ends, n, Wt.frames, Wt.host_list, Wt.counts + 1, st);
+    HIPCHK(e, hipGetLastError());
+    stamp(4);
+    Wt.frames_h.resize(n);
+    HIPCHK(e, hipMemcpyAsync(Wt.frames_h.data(), Wt.frames, (size_t)n * sizeof(kwok_watch_frame), hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipMemcpyAsync(Wt.counts_h + 1, Wt.counts + 1, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipMemcpyAsync(Wt.counts_h, Wt.ends + (n - 1), 4, hipMemcpyDeviceToHost, st));  // the last newline
+    HIPCHK(e, hipStreamSynchronize(st));
+    const uint32_t nh = Wt.counts_h[1];
+    *consumed = (size_t)Wt.counts_h[0] + 1;
+    if (nh) {  // the lines the device listed: the host framer over the caller's bytes
+        std::vector<uint32_t> list(nh);
+        HIPCHK(e, hipMemcpyAsync(list.data(), Wt.host_list, (size_t)nh * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipStreamSynchronize(st));
+        for (uint32_t i : list) {
+            if (i >= n) return e->fail(KWOK_EDEVICE, "watch framer: listed line %u of %u", i, n);
+            const uint32_t lo = Wt.frames_h[i].line_off;
+            const char* nl = (const char*)memchr(stream + lo, '\n', len - lo);
+            if (!nl) return e->fail(KWOK_EDEVICE, "watch framer: listed line %u has no end", i);
+            frame_line(stream, lo, (uint32_t)(nl - stream), &Wt.frames_h[i]);
+            HIPCHK(e, hipMemcpyAsync(Wt.frames + i, &Wt.frames_h[i], sizeof(kwok_watch_frame), hipMemcpyHostToDevice, st));
+        }
+        HIPCHK(e, hipStreamSynchronize(st));
+    }
+    int bad = 0;
+    for (uint32_t i = 0; i < n; i++) bad += Wt.frames_h[i].status != KWOK_OK;
+    memcpy(frames, Wt.frames_h.data(), (size_t)n * sizeof(kwok_watch_frame));
+    if (n_host) *n_host = nh;
+    Wt.len = len, Wt.host = stream;
+    Wt.stats[KWOK_WATCH_STAT_FRAMES] += n;
+    Wt.stats[KWOK_WATCH_STAT_HOST_FRAMES] += nh;
+    *stream_id = Wt.id = Wt.next_id++;
+    if (prof) {
+        float cs = 0, em = 0, pa = 0;
+        (void)hipEventElapsedTime(&cs, pe[1], pe[2]);
+        (void)hipEventElapsedTime(&em, pe[0], pe[3]);
+        (void)hipEventElapsedTime(&pa, pe[3], pe[4]);
+        fprintf(stderr, "[kwok watch] %zu bytes, %u frames (%u by the host): k_frame_count + k_frame_scan %.3f ms, "
+                        "k_frame_emit %.3f ms, k_frame_parse %.3f ms; the call %.2f ms\n", len, n, nh, cs, em, pa,
+                ms_between(t0, clk::now()));
+    }
+    return bad;
+}
+
+int kwok_ingest_pods_framed(kwok_engine* e, const kwok_codec* c, uint64_t stream_id, const uint32_t* frame_idx,
+                            const int32_t* handle, size_t n, int32_t* out_handles, int32_t* out_status,
+                            uint32_t* out_released, size_t* n_host) {
+    if (!e || !c || (n && (!frame_idx || !handle)) || n > 0x7FFFFFF0ull) return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    drain(e);
+    if (e->poisoned) return poisoned(e);
+    if (n_host) *n_host = 0;
+    auto& Wt = e->watch;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> len;
+    std::vector<uint8_t> op;
+    int rc = framed_records(e, stream_id, frame_idx, n, off, len, op);
+    if (rc) return rc;
+    Wt.stats[KWOK_WATCH_STAT_INGESTS]++;
+    if (!n) return 0;
+    uint32_t nh = 0;
+    if ((rc = json_decode(e, c, Wt.host, Wt.len, off.data(), len.data(), n, op.data(), handle, &nh, Wt.stream))) return rc;
+    if ((rc = json_complete(e, c, Wt.host, Wt.len, off.data(), len.data(), nh, op.data(), handle, nullptr, nullptr)))
+        return rc;
+    if (n_host) *n_host = nh;
+    ArenaSrc src(e, Wt.stream);
+    return ingest_pods_impl(e, e->ing.d_ev, 0, n, nullptr, Wt.len, out_handles, out_status, nullptr, out_released, true);
+}
+
+int kwok_ingest_nodes_framed(kwok_engine* e, const kwok_codec* c, uint64_t stream_id, const uint32_t* frame_idx,
+                             size_t n, int32_t* out_handles, int32_t* out_status, size_t* n_host) {
+    if (!e || !c || (n && !frame_idx) || n > 0x7FFFFFF0ull) return KWOK_EINVAL;
+    if (n_host) *n_host = 0;
+    auto& Wt = e->watch;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> len;
+    std::vector<uint8_t> op;
+    int rc = framed_records(e, stream_id, frame_idx, n, off, len, op);
+    if (rc) return rc;
+    Wt.stats[KWOK_WATCH_STAT_INGESTS]++;
+    ArenaSrc src(e, Wt.stream);
+    return ingest_nodes_json_impl(e, c, Wt.host, Wt.len, off.data(), len.data(), op.data(), n, out_handles, out_status,
+                                  n_host, Wt.stream);
+}
+
+int kwok_watch_stats(kwok_engine* e, uint64_t out[KWOK_WATCH_STAT_COUNT]) {
+    if (!e || !out) return KWOK_EINVAL;
+    for (int k = 0; k < KWOK_WATCH_STAT_COUNT; k++) out[k] = e->watch.stats[k];
+    return KWOK_OK;
 }
 
 int kwok_pack_pod_events(const kwok_pod_event* ev, size_t n, const char* arena, size_t arena_len, kwok_pod_rec* out,

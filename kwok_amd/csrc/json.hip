@@ -1379,3 +1379,266 @@ void launch_json_scatter(kwok_pod_event* ev, const kwok_pod_event* in, const uin
     if (n) hipLaunchKernelGGL(k_json_scatter, dim3((n + 255) / 256), dim3(256), 0, st, ev, in, list, n);
 }
 }  // namespace kwok
+
+// ---------------------------------------------------------------------------
+// the watch stream framer (kwok_watch.h, kwok_frame_watch_gpu): a watch response
+// is newline-terminated frames {"type":"MODIFIED","object":{...}}\n.
+//   line split   k_frame_count: each lane loads 16 bytes, a SWAR newline test gives
+//                a per-lane mask, its popcounts are reduced to one count per tile
+//                (KWOK_WATCH_TILE_BYTES: 256 lanes x 16 bytes x 4 steps);
+//                k_frame_scan: an exclusive scan over the tile counts, one block,
+//                KWOK_WATCH_SCAN_TILES tiles per step with a carry between steps;
+//                k_frame_emit: a second pass over the tile writes each newline's
+//                offset at base + rank (ranks in stream order: a block scan of the
+//                lanes' popcounts per step)
+//   frame parse  k_frame_parse: one thread per line, jparse with a handler that
+//                keeps the root's `type` and `object` and the object's own
+//                metadata.uid / resourceVersion / name / namespace
+// The stream buffer is padded to whole 16-byte windows past its length; a window
+// is loaded only when it starts below the length, and its bytes at or past the
+// length are masked out.
+// ---------------------------------------------------------------------------
+namespace kwok {
+namespace {
+constexpr uint32_t FR_THREADS = 256, FR_STEP = FR_THREADS * 16, FR_STEPS = KWOK_WATCH_TILE_BYTES / FR_STEP;
+static_assert(FR_STEP * FR_STEPS == KWOK_WATCH_TILE_BYTES, "a tile is whole block steps");
+
+// bit k set for each byte k of x that is a newline (the SWAR zero-byte test of str_special4)
+__device__ __forceinline__ uint32_t nl4(uint32_t x) {
+    const uint32_t y = x ^ 0x0A0A0A0Au;
+    const uint32_t m = ~(((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y | 0x7F7F7F7Fu);
+    return (((m >> 7) & 0x01010101u) * 0x01020408u) >> 24;
+}
+// the newline mask of the 16-byte window at off (bit k: byte off + k), 0 past the stream
+__device__ __forceinline__ uint32_t nl_window(const uint8_t* s, uint64_t off, uint64_t len) {
+    if (off >= len) return 0;
+    const uint4 w = *reinterpret_cast<const uint4*>(s + off);
+    uint32_t m = nl4(w.x) | nl4(w.y) << 4 | nl4(w.z) << 8 | nl4(w.w) << 12;
+    if (len - off < 16) m &= (1u << (uint32_t)(len - off)) - 1u;
+    return m;
+}
+// inclusive scan over the wave's 64 lanes
+__device__ __forceinline__ uint32_t wave_incl(uint32_t v, uint32_t lane) {
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(v, o);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+
+enum : uint8_t { F_NONE = 0, F_TYPE, F_OBJ, F_META, F_UID, F_RV, F_NAME, F_NS };
+struct FrameScan {
+    JRd* r;
+    uint8_t next = F_NONE;
+    bool err = false, host = false, root_obj = false;
+    bool in_obj = false, in_meta = false, obj_set = false;
+    uint32_t seen_root = 0, seen_obj = 0, seen_meta = 0;
+    uint8_t type = KWOK_WATCH_NONE, flags = 0;
+    jpos obj_pos = 0;
+    uint32_t obj_len = 0;
+    Span uid{0, 0}, rv{0, 0}, name{0, 0}, ns{0, 0};
+
+    __device__ uint8_t first(uint32_t& seen, int bit, uint8_t c) {
+        if (seen & (1u << bit)) return F_NONE;
+        seen |= 1u << bit;
+        return c;
+    }
+    __device__ void key(int d, const JTok& t) {
+        next = F_NONE;
+        const bool routed = d == 0 || (d == 1 && in_obj) || (d == 2 && in_meta);
+        if (!routed) return;
+        if (t.esc) {  // a routed key is compared as decoded text: the host framer decides the line
+            host = true;
+            return;
+        }
+        if (d == 0) {
+            if (lit_eq(*r, t.off, t.len, "type")) next = first(seen_root, 0, F_TYPE);
+            else if (lit_eq(*r, t.off, t.len, "object")) next = first(seen_root, 1, F_OBJ);
+        } else if (d == 1) {
+            if (lit_eq(*r, t.off, t.len, "metadata")) next = first(seen_obj, 0, F_META);
+        } else {
+            if (lit_eq(*r, t.off, t.len, "uid")) next = first(seen_meta, 0, F_UID);
+            else if (lit_eq(*r, t.off, t.len, "resourceVersion")) next = first(seen_meta, 1, F_RV);
+            else if (lit_eq(*r, t.off, t.len, "name")) next = first(seen_meta, 2, F_NAME);
+            else if (lit_eq(*r, t.off, t.len, "namespace")) next = first(seen_meta, 3, F_NS);
+        }
+    }
+    __device__ void scalar(int d, const JTok& t, bool pa) {
+        if (pa || d == 0) return;
+        if (d == 1) {
+            if (next == F_OBJ) err = true;  // object must be a JSON object
+            if (next != F_TYPE) return;
+            if (t.kind != J_STR) err = true;
+            else if (t.esc) host = true;
+            else if (lit_eq(*r, t.off, t.len, "ADDED")) type = KWOK_WATCH_ADDED;
+            else if (lit_eq(*r, t.off, t.len, "MODIFIED")) type = KWOK_WATCH_MODIFIED;
+            else if (lit_eq(*r, t.off, t.len, "DELETED")) type = KWOK_WATCH_DELETED;
+            else if (lit_eq(*r, t.off, t.len, "BOOKMARK")) type = KWOK_WATCH_BOOKMARK;
+            else if (lit_eq(*r, t.off, t.len, "ERROR")) type = KWOK_WATCH_ERROR;
+            else err = true;  // "got invalid watch event type"
+            return;
+        }
+        if (d != 3 || !in_meta || t.kind != J_STR) return;  // (a non-string value: an empty span)
+        const Span s = t.len ? Span{(uint32_t)t.off, t.len} : Span{0, 0};
+        switch (next) {
+            case F_UID: uid = s; if (t.esc) flags |= KWOK_FRAME_ESC_UID; break;
+            case F_RV: rv = s; if (t.esc) flags |= KWOK_FRAME_ESC_RV; break;
+            case F_NAME: name = s; if (t.esc) flags |= KWOK_FRAME_ESC_NAME; break;
+            case F_NS: ns = s; if (t.esc) flags |= KWOK_FRAME_ESC_NS; break;
+            default: break;
+        }
+    }
+    __device__ void begin(int d, bool a, bool pa) {
+        if (d == 0) {
+            root_obj = !a;
+            return;
+        }
+        if (pa) return;
+        if (d == 1) {
+            if (next == F_TYPE) err = true;  // type must be a string
+            if (next != F_OBJ) return;
+            if (a) err = true;
+            else in_obj = obj_set = true, obj_pos = r->pos - 1;
+        } else if (d == 2 && in_obj && next == F_META && !a) {
+            in_meta = true;
+        }
+    }
+    __device__ void end(int d, bool, bool) {
+        if (d == 1 && in_obj) in_obj = false, obj_len = (uint32_t)(r->pos - obj_pos);
+        if (d == 2) in_meta = false;
+    }
+};
+}  // namespace
+
+__global__ __launch_bounds__(FR_THREADS) void k_frame_count(const uint8_t* s, uint64_t len, uint32_t* tile_cnt) {
+    __shared__ uint32_t wsum[FR_THREADS / 64];
+    const uint64_t base = (uint64_t)blockIdx.x * KWOK_WATCH_TILE_BYTES + threadIdx.x * 16u;
+    uint32_t c = 0;
+    for (uint32_t q = 0; q < FR_STEPS; q++) c += __popc(nl_window(s, base + (uint64_t)q * FR_STEP, len));
+    for (uint32_t o = 32; o; o >>= 1) c += __shfl_down(c, o);
+    if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (uint32_t w = 0; w < FR_THREADS / 64; w++) t += wsum[w];
+        tile_cnt[blockIdx.x] = t;
+    }
+}
+
+// one block: tile_base[i] = the newlines before tile i, *total = all of them
+__global__ __launch_bounds__(KWOK_WATCH_SCAN_TILES) void k_frame_scan(const uint32_t* tile_cnt, uint32_t n_tiles,
+                                                                     uint32_t* tile_base, uint32_t* total) {
+    constexpr uint32_t NW = KWOK_WATCH_SCAN_TILES / 64;
+    static_assert(NW <= 64, "the wave totals are scanned by one wave");
+    __shared__ uint32_t wtot[NW];
+    __shared__ uint32_t carry_s;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t carry = 0;
+    for (uint32_t c0 = 0; c0 < n_tiles; c0 += KWOK_WATCH_SCAN_TILES) {
+        const uint32_t i = c0 + tid;
+        const uint32_t v = i < n_tiles ? tile_cnt[i] : 0u;
+        const uint32_t incl = wave_incl(v, lane);
+        if (lane == 63) wtot[wave] = incl;
+        __syncthreads();
+        if (wave == 0) {  // the wave totals -> their exclusive prefixes
+            const uint32_t x = lane < NW ? wtot[lane] : 0u;
+            const uint32_t xi = wave_incl(x, lane);
+            if (lane < NW) wtot[lane] = xi - x;
+        }
+        __syncthreads();
+        const uint32_t excl = carry + wtot[wave] + incl - v;
+        if (i < n_tiles) tile_base[i] = excl;
+        if (tid == KWOK_WATCH_SCAN_TILES - 1) carry_s = excl + v;
+        __syncthreads();
+        carry = carry_s;
+    }
+    if (tid == 0) *total = carry;
+}
+
+// ends[k] = the offset of the stream's k-th newline
+__global__ __launch_bounds__(FR_THREADS) void k_frame_emit(const uint8_t* s, uint64_t len, const uint32_t* tile_base,
+                                                          uint32_t* ends, uint32_t n_ends) {
+    __shared__ uint32_t wtot[2][FR_THREADS / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t run = tile_base[blockIdx.x];
+    for (uint32_t q = 0; q < FR_STEPS; q++) {
+        const uint64_t off = (uint64_t)blockIdx.x * KWOK_WATCH_TILE_BYTES + (uint64_t)q * FR_STEP + tid * 16u;
+        uint32_t m = nl_window(s, off, len);
+        const uint32_t c = __popc(m);
+        const uint32_t incl = wave_incl(c, lane);
+        if (lane == 63) wtot[q & 1][wave] = incl;  // (two sets: a step's totals are read while the next step's are written)
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+        for (uint32_t w = 0; w < FR_THREADS / 64; w++) {
+            const uint32_t t = wtot[q & 1][w];
+            if (w < wave) before += t;
+            all += t;
+        }
+        uint32_t k = run + before + incl - c;
+        while (m) {
+            const uint32_t b = (uint32_t)__builtin_ctz(m);
+            m &= m - 1;
+            if (k < n_ends) ends[k] = (uint32_t)(off + b);
+            k++;
+        }
+        run += all;
+    }
+}
+
+// one thread per line [ends[i - 1] + 1, ends[i])
+__global__ __launch_bounds__(256) void k_frame_parse(const uint8_t* s, const uint32_t* ends, uint32_t n,
+                                                     kwok_watch_frame* frames, uint32_t* host_list, uint32_t* n_host) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const jpos lo = i ? ends[i - 1] + 1u : 0u, hi = ends[i];
+    kwok_watch_frame f;
+    f.line_off = lo;
+    f.doc_off = f.doc_len = 0;
+    f.type = KWOK_WATCH_NONE, f.flags = 0, f.status = KWOK_OK, f.reserved0 = 0;
+    f.uid = f.resource_version = f.name = f.namespace_ = kwok_str{0, 0};
+    JRd rd{s, lo, hi, ~0u, make_uint4(0, 0, 0, 0)};
+    for (;;) {  // a line of only whitespace: KWOK_WATCH_NONE
+        const int c = rd.peek();
+        if (c != ' ' && c != '\t' && c != '\n' && c != '\r') break;
+        rd.pos++;
+    }
+    if (rd.pos < hi) {
+        FrameScan p;
+        p.r = &rd;
+        const bool ok = jparse(rd, p);
+        if (!ok || !p.root_obj) {
+            f.status = KWOK_EINVAL;
+        } else if (p.host) {
+            host_list[atomicAdd(n_host, 1u)] = i;  // (its frame is the host framer's)
+        } else if (p.err || p.type == KWOK_WATCH_NONE || !p.obj_set) {
+            f.status = KWOK_EINVAL;
+        } else {
+            f.type = p.type, f.flags = p.flags;
+            f.doc_off = p.obj_pos, f.doc_len = p.obj_len;
+            f.uid = kwok_str{p.uid.off, p.uid.len};
+            f.resource_version = kwok_str{p.rv.off, p.rv.len};
+            f.name = kwok_str{p.name.off, p.name.len};
+            f.namespace_ = kwok_str{p.ns.off, p.ns.len};
+        }
+    }
+    frames[i] = f;
+}
+
+void launch_frame_count(const uint8_t* s, uint64_t len, uint32_t n_tiles, uint32_t* tile_cnt, hipStream_t st) {
+    if (n_tiles) hipLaunchKernelGGL(k_frame_count, dim3(n_tiles), dim3(FR_THREADS), 0, st, s, len, tile_cnt);
+}
+void launch_frame_scan(const uint32_t* tile_cnt, uint32_t n_tiles, uint32_t* tile_base, uint32_t* total, hipStream_t st) {
+    hipLaunchKernelGGL(k_frame_scan, dim3(1), dim3(KWOK_WATCH_SCAN_TILES), 0, st, tile_cnt, n_tiles, tile_base, total);
+}
+void launch_frame_emit(const uint8_t* s, uint64_t len, uint32_t n_tiles, const uint32_t* tile_base, uint32_t* ends,
+                       uint32_t n_ends, hipStream_t st) {
+    if (n_tiles && n_ends)
+        hipLaunchKernelGGL(k_frame_emit, dim3(n_tiles), dim3(FR_THREADS), 0, st, s, len, tile_base, ends, n_ends);
+}
+void launch_frame_parse(const uint8_t* s, const uint32_t* ends, uint32_t n, kwok_watch_frame* frames, uint32_t* host_list,
+                        uint32_t* n_host, hipStream_t st) {
+    if (!n) return;
+    const uint32_t bs = json_block(n);
+    hipLaunchKernelGGL(k_frame_parse, dim3((n + bs - 1) / bs), dim3(bs), 0, st, s, ends, n, frames, host_list, n_host);
+}
+}  // namespace kwok

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/kwok_engine.h"
+#include "../../include/kwok_watch.h"
 #include "device.h"
 
 namespace kwok {
@@ -281,6 +282,19 @@ void launch_node_scatter(kwok_node_event* ev, const kwok_node_event* in, const u
 void launch_json_gather(const kwok_pod_event* ev, const JsonPodSide* side, const uint32_t* list, uint32_t n,
                         kwok_pod_event* out_ev, JsonPodSide* out_side, hipStream_t st);
 void launch_json_scatter(kwok_pod_event* ev, const kwok_pod_event* in, const uint32_t* list, uint32_t n, hipStream_t st);
+
+// ---- the watch stream framer (json.hip, kwok_watch.h): s holds len bytes and is padded
+// to whole 16-byte windows; n_tiles = ceil(len / KWOK_WATCH_TILE_BYTES) ----
+// newlines per tile
+void launch_frame_count(const uint8_t* s, uint64_t len, uint32_t n_tiles, uint32_t* tile_cnt, hipStream_t st);
+// tile_base[i] = the newlines before tile i, *total = all of them
+void launch_frame_scan(const uint32_t* tile_cnt, uint32_t n_tiles, uint32_t* tile_base, uint32_t* total, hipStream_t st);
+// ends[k] = the offset of the k-th newline (k < n_ends)
+void launch_frame_emit(const uint8_t* s, uint64_t len, uint32_t n_tiles, const uint32_t* tile_base, uint32_t* ends,
+                       uint32_t n_ends, hipStream_t st);
+// one thread per line: frames[i], or i listed for the host framer (*n_host zeroed by the caller)
+void launch_frame_parse(const uint8_t* s, const uint32_t* ends, uint32_t n, kwok_watch_frame* frames, uint32_t* host_list,
+                        uint32_t* n_host, hipStream_t st);
 
 // ---- node batches on the GPU (kwok_ingest_nodes, node_controller.go:256-270) ----
 struct NodeBatch {

@@ -112,6 +112,11 @@ def declare(lib, pre):
             "ingest_nodes_json": (C.c_int, [VP, VP, C.c_char_p, SZ, VP, VP, VP, SZ, VP, VP, P(SZ)]),
             "decode_nodes_gpu": (C.c_int, [VP, VP, VP, SZ, VP, VP, SZ, VP, VP, P(SZ)]),
             "read_wait": (C.c_int, [VP]),
+            "frame_watch": (C.c_int, [VP, SZ, VP, SZ, P(SZ), P(SZ)]),
+            "frame_watch_gpu": (C.c_int, [VP, VP, SZ, VP, SZ, P(SZ), P(SZ), P(SZ), P(U64)]),
+            "ingest_pods_framed": (C.c_int, [VP, VP, U64, VP, VP, SZ, VP, VP, VP, P(SZ)]),
+            "ingest_nodes_framed": (C.c_int, [VP, VP, U64, VP, SZ, VP, VP, P(SZ)]),
+            "watch_stats": (C.c_int, [VP, VP]),
         })
     for name, (res, args) in sig.items():
         f = getattr(lib, pre + name, None)
@@ -557,6 +562,61 @@ class Engine(EngineBase):
                                              rel.ctypes.data, C.byref(nh))
         self._check(rc, "ingest_pods_json")
         return hs, st, rel, nh.value
+
+    # ---- watch streams (include/kwok_watch.h): framed on the GPU, ingested in place ----
+    def frame_watch(self, data, cap=None):
+        """kwok_frame_watch_gpu over raw watch bytes: (frames (WATCH_FRAME_DTYPE),
+        consumed, lines the host framed, stream_id).  The stream stays resident for
+        ingest_pods_framed / ingest_nodes_framed until the next call; the engine keeps
+        a reference to the bytes (the host codec completes undecided documents from them).
+        data: bytes or a uint8 array (page-locked: host_array, for large streams)."""
+        buf = np.frombuffer(data, np.uint8) if len(data) else np.zeros(1, np.uint8)
+        n = len(data)
+        nf, used, nh, sid = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_uint64()
+        if cap is None:  # (cap: a bound on the line count the caller knows)
+            cap = bytes(data).count(b"\n") if not isinstance(data, np.ndarray) else int((data == 10).sum())
+        frames = np.zeros(max(cap, 1), abi.WATCH_FRAME_DTYPE)
+        self._watch_buf = None
+        rc = self._lib.kwok_frame_watch_gpu(self._h, buf.ctypes.data, n, frames.ctypes.data, cap, C.byref(nf),
+                                            C.byref(used), C.byref(nh), C.byref(sid))
+        self._check(rc, "frame_watch_gpu")
+        self._watch_buf = buf
+        return frames[:nf.value], used.value, nh.value, sid.value
+
+    def ingest_pods_framed(self, codec, stream_id, frame_idx, handles, out=None):
+        """kwok_ingest_pods_framed: (handles, statuses, released, documents the host decided)"""
+        idx = np.ascontiguousarray(frame_idx, np.uint32)
+        handles = np.ascontiguousarray(handles, np.int32)
+        n = len(idx)
+        if out is None:
+            hs, st, rel = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.uint32)
+        else:
+            hs, st, rel = (o[:n] for o in out)
+        nh = C.c_size_t()
+        rc = self._lib.kwok_ingest_pods_framed(self._h, codec._h, stream_id, idx.ctypes.data, handles.ctypes.data, n,
+                                               hs.ctypes.data, st.ctypes.data, rel.ctypes.data, C.byref(nh))
+        self._check(rc, "ingest_pods_framed")
+        return hs, st, rel, nh.value
+
+    def ingest_nodes_framed(self, codec, stream_id, frame_idx, out=None):
+        """kwok_ingest_nodes_framed: (handles, statuses, documents the host decided)"""
+        idx = np.ascontiguousarray(frame_idx, np.uint32)
+        n = len(idx)
+        if out is None:
+            hs, st = np.empty(n, np.int32), np.empty(n, np.int32)
+        else:
+            hs, st = (o[:n] for o in out)
+        nh = C.c_size_t()
+        rc = self._lib.kwok_ingest_nodes_framed(self._h, codec._h, stream_id, idx.ctypes.data, n, hs.ctypes.data,
+                                                st.ctypes.data, C.byref(nh))
+        self._check(rc, "ingest_nodes_framed")
+        return hs, st, nh.value
+
+    def watch_stats(self):
+        """kwok_watch_stats: frames framed / of them by the host / stream bytes uploaded / framed ingest calls"""
+        out = (C.c_uint64 * len(abi.WATCH_STATS))()
+        self._check(self._lib.kwok_watch_stats(self._h, out), "watch_stats")
+        return dict(zip(abi.WATCH_STATS, list(out)))
 
     @staticmethod
     def _arena_arg(arena):
