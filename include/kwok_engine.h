@@ -487,14 +487,18 @@ int kwok_profile_read(kwok_engine* e, double ms_sum[KWOK_T_COUNT], uint64_t* tic
  * waiting for the device, host bookkeeping after the wait, whole call. */
 enum { KWOK_H_ENQUEUE = 0, KWOK_H_WAIT, KWOK_H_POST, KWOK_H_TOTAL, KWOK_H_COUNT };
 int kwok_profile_host(kwok_engine* e, int reset, double ms_sum[KWOK_H_COUNT], uint64_t* ticks);
-/* Which tick kernel ran (diagnostics, tests): heartbeat-once ticks expected to
- * have nothing to emit run a counting kernel (k_once); one that had work after
- * all runs again with the full tick kernel.  Counts since create. */
-enum { KWOK_STAT_TICKS_FULL = 0 /* ticks run by the full tick kernel (redone ticks included) */,
-       KWOK_STAT_TICKS_ONCE /* heartbeat-once ticks completed by the counting kernel */,
-       KWOK_STAT_ONCE_REDO /* counting-kernel ticks that had work and ran again with the full kernel */,
-       KWOK_STAT_ONCE_SUMMARY /* counting-kernel launches that read the per-bucket summaries, not the pod rows */,
+/* Which tick kernel ran (diagnostics, tests): single-rank ticks expected to
+ * have nothing to emit run a counting kernel - alone on a heartbeat-once
+ * engine (k_once), beside the heartbeat streamers in one launch on an engine
+ * that writes every body (k_once_stream; such a tick counts under TICKS_FULL
+ * as well); one that had work after all runs again with the full tick kernel.
+ * Counts since create. */
+enum { KWOK_STAT_TICKS_FULL = 0 /* ticks that wrote every body: the full tick kernel (redone ticks included), k_once_stream */,
+       KWOK_STAT_TICKS_ONCE /* heartbeat-once ticks completed by the counting kernel alone */,
+       KWOK_STAT_ONCE_REDO /* counting-kernel ticks (either kind) that had work and ran again with the full kernel */,
+       KWOK_STAT_ONCE_SUMMARY /* counting-kernel launches (either kind) that read the per-bucket summaries, not the pod rows */,
        KWOK_STAT_TICKS_HB_DELTA /* ticks whose heartbeat stream rewrote only the lines that changed (KWOK_HB_DELTA) */,
+       KWOK_STAT_TICKS_ONCE_STREAM /* quiet ticks completed by the counting kernel beside the streamers (KWOK_ONCE_STREAM) */,
        KWOK_STAT_COUNT };
 int kwok_engine_stats(const kwok_engine* e, uint64_t out[KWOK_STAT_COUNT]);
 

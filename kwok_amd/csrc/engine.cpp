@@ -352,7 +352,8 @@ struct kwok_engine {
         bool fuse = false;          // ... and writes their patch bytes itself (DevState::fuse_pods)
         bool inits_folded = false;  // ... and the node inits' too (no k_emit launch: KWOK_FOLD_INITS)
         bool quiet = false;         // only pods with an event are Use-checked (kwok_engine::quiet)
-        bool once = false;          // launched as k_once (a heartbeat-once tick expected to have nothing to emit)
+        bool once = false;          // launched as k_once / k_once_stream (a tick expected to have nothing to emit)
+        bool once_stream = false;   // ... as k_once_stream: the engine writes every heartbeat body
         bool once_use = false;      // ... reading the per-bucket summaries (counted when it retires as a once tick)
         hipEvent_t rd = nullptr;    // kwok_read_arena_async: the last read queued from this slot's arena
         bool rd_pending = false;    //   (a submit or an arena growth that takes the slot waits for it)
@@ -361,7 +362,7 @@ struct kwok_engine {
         // What the heartbeat region [0, n x stride) of `arena` provably holds: n complete
         // bodies of the template generation `gen` at `clock`.  Written by retire alone,
         // for a tick that completed without error, was not skipped on the device or
-        // requeued, was no k_once tick and ran its stream; cleared by everything that
+        // requeued, was not redone after k_once_stream found work and ran its stream; cleared by everything that
         // replaces, poisons or is about to overwrite the arena (grow_arena, alloc_slot,
         // every enqueue, so also a failed tick and the debug layout-fault tick) and by a
         // template change.  A tick whose layout matches it exactly writes only the lines
@@ -409,6 +410,7 @@ struct kwok_engine {
     int xspec_env = -1;                 // KWOK_XSPEC: 0 off, N: ticks kept on after a long-list tick (default 256)
     uint64_t xspec_miss = 0;  // diagnostics: speculative ticks whose lists did not fit
     uint32_t n_stream = 0;      // k_tick heartbeat streamer blocks (the chain blocks: S.n_chain)
+    uint32_t n_once_stream = 0; // k_once_stream's streamer blocks (512 threads each; KWOK_ONCE_STREAMERS), 0: by size
     uint32_t emit_grid = 0;     // k_emit blocks
     bool emit_hint = true;      // events were ingested since the last submit: the tick likely emits patches
     bool sync_spin = true;      // spin on a tick's completion event (KWOK_SYNC=spin, the default)
@@ -437,7 +439,13 @@ struct kwok_engine {
     bool foreign_ips = false;   // sticky: a podIP not assigned by this engine entered the pool
     bool global_foreign = false;  // multi rank, sticky: some rank's exchange message carried its foreign_ips
     bool quiet_ok = true;
-    bool once_ok = true;        // KWOK_ONCE=0: heartbeat-once ticks always run k_tick (A/B)
+    bool once_ok = true;        // KWOK_ONCE=0: quiet ticks always run k_tick (A/B)
+    bool once_stream_ok = true; // KWOK_ONCE_STREAM=0: ... those of engines that write every body (A/B; k_once stays)
+    // the last retired tick patched pods that took no address in it (created with an empty
+    // status: patched without IPs, their Gets follow in the next tick): that tick is not
+    // quiet, whatever the events say.  k_once_stream's prediction only: a redone tick
+    // writes its whole stream again, k_tick here writes the changed lines
+    bool pp_followup = false;
     // k_once's per-bucket summaries (DevState::once_sum): valid while nothing has changed a
     // pod state since the BUILD tick of generation sum_gen was enqueued (every ingest, CNI
     // assignment, pool Put, zombie sweep and k_tick launch clears sum_valid)
@@ -1338,7 +1346,8 @@ int kwok_engine_create(const kwok_config* cfg, kwok_engine** out) {
             S.n_pool_extra = (uint32_t)std::min<int64_t>(std::max(0, atoi(v)), std::min<int64_t>((int64_t)cus * occ - S.n_chain, e->n_stream));
         e->emit_grid = (uint32_t)(cus * std::max(1, std::min(emit_occupancy(), 8)));
         if (const char* v = getenv("KWOK_EMIT_BLOCKS_PER_CU")) e->emit_grid = (uint32_t)(cus * std::max(1, std::min(atoi(v), 8)));
-        if (const char* v = getenv("KWOK_TICK_STREAMERS")) e->n_stream = (uint32_t)std::max(1, atoi(v));
+        if (const char* v = getenv("KWOK_TICK_STREAMERS")) e->n_stream = e->n_once_stream = (uint32_t)std::max(1, atoi(v));
+        if (const char* v = getenv("KWOK_ONCE_STREAMERS")) e->n_once_stream = (uint32_t)std::max(1, atoi(v));
         const char* pr = getenv("KWOK_TICK_PRIO");
         e->chain_prio = pr && pr[0] == '1';
         if (const char* v = getenv("KWOK_TICK_STREAM_DELAY_NS")) S.stream_delay = (uint32_t)std::max(0, atoi(v) / 10);
@@ -1370,6 +1379,8 @@ int kwok_engine_create(const kwok_config* cfg, kwok_engine** out) {
         e->fold_inits = !(fi && fi[0] == '0');
         const char* on = getenv("KWOK_ONCE");
         e->once_ok = !(on && on[0] == '0');
+        const char* ost = getenv("KWOK_ONCE_STREAM");
+        e->once_stream_ok = !(ost && ost[0] == '0');
         const char* os = getenv("KWOK_ONCE_SUM");
         e->once_sum_ok = !(os && os[0] == '0');
         const char* zc = getenv("KWOK_INGEST_ZC");
@@ -1429,7 +1440,7 @@ int kwok_engine_create(const kwok_config* cfg, kwok_engine** out) {
         (rc = dalloc(e, &S.wc_pre, (size_t)S.n_chain * MAX_WC)) ||
         (rc = dalloc(e, &S.wc_dirty, (size_t)S.n_chain * WC_DIRTY_WORDS)) || (rc = dalloc(e, &S.jbase, (size_t)S.n_chain)) ||
         (e->sparse_jobs && (rc = dalloc(e, &S.gjob, (size_t)S.n_chain * MAX_WC * WC_GROUPS))) ||
-        (getenv("KWOK_TICK_TRACE") && (rc = dalloc(e, &S.trace, (size_t)(S.n_chain + e->n_stream) * TRACE_SLOTS))) ||
+        (getenv("KWOK_TICK_TRACE") && (rc = dalloc(e, &S.trace, (size_t)(S.n_chain + std::max(2 * e->n_stream, e->n_once_stream)) * TRACE_SLOTS))) ||
         (getenv("KWOK_JOBS_TRACE") && (rc = dalloc(e, &S.jtrace, (size_t)S.n_chain * (MAX_WC + 4) * 4))) ||
         (rc = dalloc(e, &S.alloc_addr, PLa)) || (rc = dalloc(e, (uint8_t**)&S.hb_static, HB_MAX_STRIDE)) ||
         (rc = dalloc(e, (uint8_t**)&S.hb_kind, HB_MAX_STRIDE)) ||
@@ -3208,9 +3219,21 @@ int enqueue_tick(kwok_engine* e, int k, bool requeue) {
     T.inits_folded = false;  // (set where k_pod_jobs is launched)
     // ... and leave the whole stream to the streamers: a dirty chain block's share
     // of it would hold up the pool phase, which waits for every dirty block
+    // a tick expected to have nothing to emit (no events since the previous tick, quiet
+    // Use checks) is counted by k_once: one wave per bucket, every load of the bucket in
+    // flight at once.  One that has work after all is run again with k_tick by retire
+    // (TickHdr::redo; a launch queued behind it skips).  A heartbeat-once engine's is
+    // k_once alone; an engine that writes every body runs k_once_stream, the same count
+    // beside the heartbeat streamers (KWOK_ONCE_STREAM=0: k_tick, for A/B)
+    if (!requeue) T.no_once = false;
+    T.once = !e->multi && e->once_ok && !T.emit_queued && !T.split && T.quiet && !T.no_once &&
+             S.cn <= (uint32_t)ONCE_NODE_LDS && e->PL < (1u << ONCE_FIELD_BITS) && e->NL < (1u << ONCE_FIELD_BITS) &&
+             (S.hb_once || (e->once_stream_ok && e->n_stream > 0 && !e->no_stream && !e->pp_followup));
+    T.once_stream = T.once && !S.hb_once;
+    // (k_once_stream's counting blocks are done in ~10 us: the stream is the streamers')
     S.stream_share = e->n_stream == 0 ? 0u
                      : e->share_env >= 0 ? (uint32_t)e->share_env
-                                         : (hb_bytes < (32ull << 20) || T.split || T.hb_prev ? 1024u
+                                         : (hb_bytes < (32ull << 20) || T.split || T.hb_prev || T.once_stream ? 1024u
                                             : S.hb_nt                                        ? 860u
                                                                                              : 921u);
     S.use_events_only = T.quiet ? 1u : 0u;
@@ -3221,19 +3244,12 @@ int enqueue_tick(kwok_engine* e, int k, bool requeue) {
     const int prof = (ev ? TICK_PROF : 0) | (e->chain_prio ? TICK_PRIO : 0) | (e->no_stream ? TICK_NOSTREAM : 0) |
                      (T.split ? TICK_SPLIT : 0);
     if (!requeue) {
-        T.no_once = false;
         memset(T.hdr_h, 0, sizeof(TickHdr));  // the slot's previous tick was collected
         if (++e->tick_tag == 0) e->tick_tag = 1;
         T.tag = e->tick_tag;
         T.target = ++e->front_launches * S.n_chain;
     }
     const uint64_t now = T.now;
-    // a heartbeat-once tick expected to have nothing to emit (no events since the
-    // previous tick, quiet Use checks) runs k_once: one wave per bucket, every load
-    // of the bucket in flight at once.  One that has work after all is run again
-    // with k_tick by retire (TickHdr::redo; a launch queued behind it skips)
-    T.once = !e->multi && S.hb_once && e->once_ok && !T.emit_queued && !T.split && T.quiet && !T.no_once &&
-             S.cn <= (uint32_t)ONCE_NODE_LDS && e->PL < (1u << ONCE_FIELD_BITS) && e->NL < (1u << ONCE_FIELD_BITS);
     if (T.once) {
         // per-bucket summaries: BUILD them on the first once tick after a change, USE them after
         uint32_t mode = ONCE_SUM_OFF;
@@ -3247,8 +3263,16 @@ int enqueue_tick(kwok_engine* e, int k, bool requeue) {
             }
         }
         T.once_use = mode == ONCE_SUM_USE;
-        launch_tick_once(S, now, (uint64_t)e->start, nhb, prof & TICK_PROF, mode, e->sum_gen, st, ev ? ev[0] : nullptr,
-                         ev ? ev[1] : nullptr);
+        // k_once_stream's 512-thread streamer blocks: one per CU, two (16 streaming waves) for a
+        // region past the Infinity Cache (hb_nt's size).  1M x 10M: 0.1146 ms per step with one,
+        // 0.1088 with two; 100k x 1M: 0.0156 with one, 0.0177 with two (profiles/q1_layout_ab.txt)
+        const uint32_t n_os = e->n_once_stream ? e->n_once_stream : hb_bytes >= (256ull << 20) ? 2 * e->n_stream : e->n_stream;
+        if (T.once_stream)
+            launch_tick_once_stream(S, n_os, now, (uint64_t)e->start, nhb, prof & (TICK_PROF | TICK_NOSTREAM), mode,
+                                    e->sum_gen, T.hb_prev, st, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr);
+        else
+            launch_tick_once(S, now, (uint64_t)e->start, nhb, prof & TICK_PROF, mode, e->sum_gen, st, ev ? ev[0] : nullptr,
+                             ev ? ev[1] : nullptr);
         HIPCHK(e, hipGetLastError());
         qstamp(2);
     } else if (!e->multi) {
@@ -3671,10 +3695,12 @@ int retire(kwok_engine* e) {
     e->host_ms[KWOK_H_POST] += ms_between(t2, t3);
     e->host_ms[KWOK_H_TOTAL] += ms_between(t1, t3);
     e->host_ticks++;
-    e->stats[T.once ? KWOK_STAT_TICKS_ONCE : KWOK_STAT_TICKS_FULL]++;
+    e->stats[T.once && !T.once_stream ? KWOK_STAT_TICKS_ONCE : KWOK_STAT_TICKS_FULL]++;
+    if (T.once_stream) e->stats[KWOK_STAT_TICKS_ONCE_STREAM]++;
+    e->pp_followup = !e->S.cni && H.n_pp != H.n_alloc_local;
     // the slot's heartbeat region now holds this tick's bodies (TickSlot::HbValid); a
-    // tick that was a k_once tick at any point (redone ones included) records nothing
-    if (T.hb_record && !T.once && !T.no_once) {
+    // tick that was redone records nothing (hb_record: no heartbeat-once engine, no requeue)
+    if (T.hb_record && !T.no_once) {
         kwok_engine::TickSlot::HbValid& V = T.hb_valid;
         V.arena = T.arena, V.n = T.hb_n, V.stride = e->hb_stride, V.units = e->S.hb_units, V.gen = e->hb_gen;
         V.clock = T.now;

@@ -178,6 +178,12 @@ void launch_tick(const DevState& S, uint32_t n_stream, uint64_t now, uint64_t st
 void launch_tick_once(const DevState& S, uint64_t now, uint64_t start, uint32_t n_hb, int phases, uint32_t sum_mode,
                       uint32_t gen, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 uint32_t once_blocks(const DevState& S);
+// the same quiet tick on an engine that writes every heartbeat body (single rank):
+// n_stream streamer blocks (the whole stream, or with hb_prev its changed lines, as
+// launch_tick's) and the counting blocks in one launch; phases: TICK_PROF, TICK_NOSTREAM
+void launch_tick_once_stream(const DevState& S, uint32_t n_stream, uint64_t now, uint64_t start, uint32_t n_hb, int phases,
+                             uint32_t sum_mode, uint32_t gen, uint64_t hb_prev, hipStream_t st, hipEvent_t t0 = nullptr,
+                             hipEvent_t t1 = nullptr);
 // split ticks: the pod jobs (deletes, patch job records, state transitions) of
 // every dirty 64-group run of every chain block, one wave each
 // k_pod_jobs; a fused launch (DevState::fuse_pods) also writes the node inits with init_blocks blocks

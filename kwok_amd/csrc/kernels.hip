@@ -1552,6 +1552,8 @@ static_assert(HB_GROUP_UNITS > 256 && HB_GROUP_UNITS <= 320, "5 stores of a wave
 static_assert(HB_GROUP_SLOTS * HB_MAX_UNITS <= 320, "custom heartbeats: still 5 stores of a wave per group");
 // A custom heartbeat (any 16-byte unit count up to HB_MAX_UNITS): the same
 // group walk with the unit count a launch argument, every store predicated.
+// NT: the block's thread count (k_tick and k_emit: BLOCK; k_once_stream: 64 * ONCE_WAVES)
+template <int NT = BLOCK>
 __device__ __noinline__ void hb_fill_groups_any(const DevState& S, const uint4* tmpl, uint64_t n_hb, uint64_t g0,
                                                 uint64_t g1) {
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -1564,7 +1566,7 @@ __device__ __noinline__ void hb_fill_groups_any(const DevState& S, const uint4* 
     }
     const uint64_t units = n_hb * U;
     u32x4* dst = reinterpret_cast<u32x4*>(S.arena);
-    for (uint64_t g = g0 + w; g < g1; g += BLOCK / 64) {
+    for (uint64_t g = g0 + w; g < g1; g += NT / 64) {
         const uint64_t u0 = g * GU + l;
         u32x4* p = dst + u0;
         if (S.hb_nt) {
@@ -1581,11 +1583,11 @@ __device__ __noinline__ void hb_fill_groups_any(const DevState& S, const uint4* 
 // groups [g0, g1) of the heartbeat region (units past n_hb slots are not written).
 // GEN: a custom heartbeat geometry (k_tick<true>); the default one compiles
 // without the general walk so its register allocation is untouched.
-template <bool GEN>
+template <bool GEN, int NT = BLOCK>
 __device__ __forceinline__ void hb_fill_groups(const DevState& S, const uint4* tmpl, uint64_t n_hb, uint64_t g0,
                                                uint64_t g1) {
     if (GEN) {
-        hb_fill_groups_any(S, tmpl, n_hb, g0, g1);
+        hb_fill_groups_any<NT>(S, tmpl, n_hb, g0, g1);
         return;
     }
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -1598,7 +1600,7 @@ __device__ __forceinline__ void hb_fill_groups(const DevState& S, const uint4* t
     }
     const uint64_t units = n_hb * HB_CHUNKS;
     u32x4* dst = reinterpret_cast<u32x4*>(S.arena);  // heartbeat region starts at arena offset 0
-    for (uint64_t g = g0 + w; g < g1; g += BLOCK / 64) {
+    for (uint64_t g = g0 + w; g < g1; g += NT / 64) {
         const uint64_t u0 = g * HB_GROUP_UNITS + l;
         u32x4* p = dst + u0;
         if (S.hb_nt && u0 + 256u < units) {  // a whole group, non-temporal (S.hb_nt: uniform)
@@ -1627,19 +1629,20 @@ __device__ __forceinline__ bool hb_share_any(const DevState& S, uint64_t n_hb, u
     const uint64_t cut = groups * S.stream_share / 1024, n = groups - cut;
     return n * idx / cnt < n * (idx + 1) / cnt;
 }
-template <bool GEN>
+template <bool GEN, int NT = BLOCK>
 __device__ __forceinline__ void hb_fill_share(const DevState& S, const uint4* tmpl, uint64_t n_hb, bool streamer,
                                               uint32_t idx, uint32_t cnt) {
     const uint64_t groups = (n_hb + HB_GROUP_SLOTS - 1) / HB_GROUP_SLOTS;
     const uint64_t cut = groups * S.stream_share / 1024;
     const uint64_t lo = streamer ? 0 : cut, n = streamer ? cut : groups - cut;
-    hb_fill_groups<GEN>(S, tmpl, n_hb, lo + n * idx / cnt, lo + n * (idx + 1) / cnt);
+    hb_fill_groups<GEN, NT>(S, tmpl, n_hb, lo + n * idx / cnt, lo + n * (idx + 1) / cnt);
 }
 
 // per-tick heartbeat template in LDS: static bytes + Now / StartTime slots
+template <int NT = BLOCK>
 __device__ __forceinline__ void build_hb_template(const DevState& S, uint8_t* tmpl, uint64_t now_unix, uint64_t start_unix) {
     const Ts now = format_ts(now_unix), st = format_ts(start_unix);
-    for (int i = threadIdx.x; i < (int)(16u * S.hb_units); i += BLOCK) {
+    for (int i = threadIdx.x; i < (int)(16u * S.hb_units); i += NT) {
         const uint8_t k = S.hb_kind[i];
         uint32_t b;
         if (k == 0xFF) b = S.hb_static[i];
@@ -1671,17 +1674,18 @@ static_assert(HB_GROUP_SLOTS * HB_MAX_UNITS <= 512 && HB_MAX_UNITS <= 128, "HbDe
 // groups [g0, g1) of the heartbeat region: tmpl holds the new template (build_hb_template).
 // Every (group, dirty unit) pair is one item of a flat walk, so every lane stores
 // whatever the number of dirty lines; units past n_hb slots are not written.
+template <int NT = BLOCK>
 __device__ __forceinline__ void hb_fill_delta(const DevState& S, const uint4* tmpl, HbDelta* D, uint64_t prev_unix,
                                            uint64_t n_hb, uint64_t g0, uint64_t g1) {
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     const uint32_t t = threadIdx.x, U = S.hb_units, GU = HB_GROUP_SLOTS * U;
-    for (uint32_t i = t; i < (uint32_t)HB_MAX_UNITS; i += BLOCK) D->mark[i] = 0;
+    for (uint32_t i = t; i < (uint32_t)HB_MAX_UNITS; i += NT) D->mark[i] = 0;
     __syncthreads();
     // the previous template's bytes against the new one's: Now values only (the static
     // bytes and StartTime are fixed at create); no step of the clock is assumed
     const Ts prev = format_ts(prev_unix);
     const uint8_t* tb = reinterpret_cast<const uint8_t*>(tmpl);
-    for (uint32_t i = t; i < 16u * U; i += BLOCK) {
+    for (uint32_t i = t; i < 16u * U; i += NT) {
         const uint8_t k = S.hb_kind[i];
         if (k < TS_LEN && ts_byte(prev, k) != tb[i]) D->mark[i >> 4] = 1;
     }
@@ -1707,7 +1711,7 @@ __device__ __forceinline__ void hb_fill_delta(const DevState& S, const uint4* tm
     if (n_e == 0 || g0 >= g1) return;  // (the same clock twice: nothing to write)
     const uint64_t units = n_hb * U;
     u32x4* dst = reinterpret_cast<u32x4*>(S.arena);
-    const uint32_t dg = (uint32_t)BLOCK / n_e, dr = (uint32_t)BLOCK % n_e;
+    const uint32_t dg = (uint32_t)NT / n_e, dr = (uint32_t)NT % n_e;
     uint64_t g = g0 + t / n_e;
     uint32_t r = t % n_e;
     const bool nt = S.hb_nt != 0;
@@ -1726,17 +1730,17 @@ __device__ __forceinline__ void hb_fill_delta(const DevState& S, const uint4* tm
     }
 }
 // this block's share of the stream (hb_fill_share's split), full or delta
-template <bool GEN>
+template <bool GEN, int NT = BLOCK>
 __device__ __forceinline__ void hb_write_share(const DevState& S, const uint4* tmpl, HbDelta* D, uint64_t prev_unix,
                                                uint64_t n_hb, bool streamer, uint32_t idx, uint32_t cnt) {
     if (prev_unix == 0) {
-        hb_fill_share<GEN>(S, tmpl, n_hb, streamer, idx, cnt);
+        hb_fill_share<GEN, NT>(S, tmpl, n_hb, streamer, idx, cnt);
         return;
     }
     const uint64_t groups = (n_hb + HB_GROUP_SLOTS - 1) / HB_GROUP_SLOTS;
     const uint64_t cut = groups * S.stream_share / 1024;
     const uint64_t lo = streamer ? 0 : cut, n = streamer ? cut : groups - cut;
-    hb_fill_delta(S, tmpl, D, prev_unix, n_hb, lo + n * idx / cnt, lo + n * (idx + 1) / cnt);
+    hb_fill_delta<NT>(S, tmpl, D, prev_unix, n_hb, lo + n * idx / cnt, lo + n * (idx + 1) / cnt);
 }
 
 // ---------------------------------------------------------------------------
@@ -2729,199 +2733,65 @@ __device__ __forceinline__ void once_group_both(const uint32_t (&stw)[4], uint32
 template <bool CNI, uint32_t SUM>  // SUM: ONCE_SUM_OFF / _BUILD / _USE (each its own registers)
 __global__ __launch_bounds__(64 * ONCE_WAVES, 2) void k_once(DevState S, uint64_t now_unix, uint64_t start_unix,
                                                             uint32_t n_hb, int phases, uint32_t gen) {
-    __shared__ uint32_t nfl32[ONCE_WAVES][ONCE_NODE_LDS / 4];  // the bucket's node tick flags, per wave
-    __shared__ uint64_t part[ONCE_WAVES][ONCE_ACC_WORDS];
-    __shared__ uint8_t tmpl[16 * HB_MAX_UNITS];
-    const uint32_t t = threadIdx.x, l = t & 63u, w = (uint32_t)wave_id(), b = blockIdx.x;
-    if (ld32_sc1(&S.bar->skip)) return;  // queued behind a tick the host must finish (re-enqueued then)
-    const bool stamp = S.trace && t == 0 && b < S.n_chain;
-#define OSTAMP(k) \
-    if (stamp) S.trace[(size_t)b * TRACE_SLOTS + (k)] = __builtin_amdgcn_s_memrealtime()
-    OSTAMP(0);
-    // profiled ticks: the earliest start, from the first block of each XCD (512 adds to one
-    // word would serialise ~6 us into the kernel)
-    if ((phases & TICK_PROF) && t == 0 && b < 8u)
-        atomicMax(&S.bar->neg_entry_max, ~(unsigned long long)__builtin_amdgcn_s_memrealtime());
-    const uint32_t bk = b * ONCE_WAVES + w;
-    uint32_t hb = 0, lock = 0, mng = 0, rdy = 0, ev = 0, tot = 0, pnd = 0, run = 0, rare = 0;
-    uint32_t be0 = 0, be1 = 0, br0 = 0, br1 = 0;  // SUM == ONCE_SUM_BUILD: eval / rare under both uniform flags
-    if (bk < S.nb) {  // (wave-uniform)
-        const uint32_t cn = S.cn, cp = S.cp;
-        const uint32_t fill = min((uint32_t)S.pod_fill[bk], cp);
-        // ---- every load of the bucket: node bytes first (classified first), pod state rows
-        const uint8_t* nst = S.node_state + (size_t)bk * cn;
-        uint32_t nw[ONCE_NODE_WORDS];
-#pragma unroll
-        for (int c = 0; c < ONCE_NODE_WORDS; c++) {
-            const uint32_t i = 4u * (l + 64u * c);
-            nw[c] = 0;
-            if (256u * c < cn && i < cn) nw[c] = *reinterpret_cast<const uint32_t*>(nst + i);
+#define ONCE_B blockIdx.x
+#define ONCE_G gridDim.x
+    constexpr bool ONCE_BODY = true;
+#include "once_count.inc"
+#undef ONCE_B
+#undef ONCE_G
+}
+
+// ---------------------------------------------------------------------------
+// k_once_stream: the quiet tick of a single-rank engine that writes every
+// heartbeat body.  No pod or node state has changed since the previous tick, so
+// the count is k_once's (summaries included) and the bodies are all one template:
+// the stream needs n_hb, the two clocks and the template, nothing from the count.
+// One launch, two kinds of 512-thread blocks: n_stream streamers at the low block
+// indices (dispatched first: the stream is the long part; a counting block is
+// done in ~10 us and two blocks share a CU), then once_blocks() counting blocks,
+// which write the rest of the stream after their arrival when stream_share
+// leaves them one (hb_write_share's split, as k_tick's chain blocks).  A
+// streamer writes whole new bodies whether or not the count finds work: the host
+// runs a redone tick's whole stream again with k_tick.
+// ---------------------------------------------------------------------------
+template <bool CNI, uint32_t SUM, bool GEN_HB>
+__global__ __launch_bounds__(64 * ONCE_WAVES, 2) void k_once_stream(DevState S, uint64_t now_unix, uint64_t start_unix,
+                                                                   uint32_t n_hb, int phases, uint32_t gen,
+                                                                   uint64_t prev_unix, uint32_t n_stream) {
+    constexpr int NT = 64 * ONCE_WAVES;
+    __shared__ uint4 hb_tmpl4[HB_MAX_UNITS];
+    __shared__ HbDelta hb_delta;  // prev_unix != 0: the stream's dirty lines (hb_fill_delta)
+    uint8_t* hb_tmpl = reinterpret_cast<uint8_t*>(hb_tmpl4);
+    const uint32_t t = threadIdx.x, b = blockIdx.x;
+    if (b < n_stream) {
+        if (ld32_sc1(&S.bar->skip)) return;  // (the counting blocks' check: the whole launch skips)
+        if (S.trace && t == 0) S.trace[(size_t)(S.n_chain + b) * TRACE_SLOTS] = __builtin_amdgcn_s_memrealtime();
+        if ((phases & TICK_PROF) && t == 0 && b < 8u)  // (dispatched before the counting blocks)
+            atomicMax(&S.bar->neg_entry_max, ~(unsigned long long)__builtin_amdgcn_s_memrealtime());
+        build_hb_template<NT>(S, hb_tmpl, now_unix, start_unix);
+        if (!(phases & TICK_NOSTREAM))
+            hb_write_share<GEN_HB, NT>(S, hb_tmpl4, &hb_delta, prev_unix, hb_bodies(S, n_hb), true, b, n_stream);
+        if ((phases & TICK_PROF) && t == 0) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            atomicMax(&S.bar->stream_end_max, (unsigned long long)__builtin_amdgcn_s_memrealtime());
         }
-        const uint16_t* pst = S.pod_state + (size_t)bk * cp;
-        constexpr bool use = SUM == ONCE_SUM_USE;
-        uint4 sm = make_uint4(0, 0, 0, 0), st[ONCE_ROWS];
-        if (use) sm = S.once_sum[bk];  // (one address: one request)
-#pragma unroll
-        for (int r = 0; r < ONCE_ROWS; r++) {
-            const uint32_t g8 = 8u * (l + 64u * r);
-            st[r] = make_uint4(0, 0, 0, 0);
-            if (!use && g8 < (r < ONCE_SPEC_ROWS ? cp : fill)) st[r] = *reinterpret_cast<const uint4*>(pst + g8);
-        }
-        // ---- nodes: LockNode / configureNode (A.5), heartbeat handles, re-lock flags
-        uint32_t or0 = 0, and0 = 1, has = 0, base = S.hb_bpre[bk];
-#pragma unroll
-        for (int c = 0; c < ONCE_NODE_WORDS; c++) {
-            if (256u * c < cn) {  // (uniform)
-                const uint32_t word = nw[c], i0 = 4u * (l + 64u * c);
-                uint32_t tickw = 0, m = 0;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const uint8_t s = (uint8_t)(word >> (8 * k));
-                    const NodeCls nc = classify_node(s);
-                    hb += nc.hb;
-                    lock += nc.lock;
-                    mng += nc.managed;
-                    rdy += nc.ready;
-                    rare |= (nc.init || (s & NS_EVENT_LOCK)) ? 1u : 0u;
-                    const uint32_t f = node_tick_flags(s);
-                    tickw |= f << (8 * k);
-                    if (s) or0 |= f & 1u, and0 &= f & 1u, has = 1;
-                    m += (uint32_t)nc.managed << k;
-                }
-                if (i0 < cn) nfl32[w][l + 64u * c] = tickw;
-                // KeepNodeHeartbeat's handles, node order: the wave's managed nodes of this word
-                const uint32_t cnt = (uint32_t)__popc(m), inc = wave_incl_scan(cnt);
-                uint32_t pos = base + inc - cnt;
-                for (uint32_t mm = m; mm; mm &= mm - 1) {
-                    if (pos < S.n_node_slots)
-                        S.hb_nodes[pos] = S.node_handle_base + (int32_t)((size_t)bk * cn + i0 + (uint32_t)__builtin_ctz(mm));
-                    pos++;
-                }
-                base += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-            }
-        }
-        // a pod's node matters only if the bucket's node entries disagree on RELOCK
-        const bool any_set = __ballot(has && or0) != 0, any_clr = __ballot(has && !and0) != 0;
-        const bool uni = !(any_set && any_clr);
-        const uint8_t u = any_set ? (uint8_t)NT_RELOCK : (uint8_t)0;
-        OSTAMP(8);
-        const uint16_t* pnd_ = S.pod_node + (size_t)bk * cp;
-        // ---- pods: needLockPod / computePatchData, counted (once_group)
-        auto count_row = [&](uint32_t g8, const uint4& s4, const uint32_t (&rl)[4]) {
-            const bool in = g8 < fill;
-            const uint32_t stw[4] = {in ? s4.x : 0u, in ? s4.y : 0u, in ? s4.z : 0u, in ? s4.w : 0u};
-            rare |= once_group<CNI>(stw, rl, ev, tot, pnd, run);
-            if constexpr (SUM == ONCE_SUM_BUILD) once_group_both<CNI>(stw, be0, be1, br0, br1);
-        };
-        auto lds_flags = [&](const uint4& n4, uint32_t (&rl)[4]) {
-            const uint8_t* nfw = reinterpret_cast<const uint8_t*>(nfl32[w]);
-            const uint32_t q[4] = {n4.x, n4.y, n4.z, n4.w};
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const uint32_t a = nfw[min(q[k] & 0xFFFFu, (uint32_t)ONCE_NODE_LDS - 1u)];
-                const uint32_t c = nfw[min(q[k] >> 16, (uint32_t)ONCE_NODE_LDS - 1u)];
-                rl[k] = a | c << 16;  // (NT_RELOCK is bit 0)
-            }
-        };
-        if (use && uni && sm.w == gen) {  // the bucket's summary (lane 0's counts; rare from any lane)
-            if (l == 0) {
-                ev += u ? sm.x >> 16 : sm.x & 0xFFFFu;
-                tot += sm.y & 0xFFFFu, pnd += sm.y >> 16, run += sm.z & 0xFFFFu;
-            }
-            rare |= (sm.z >> (u ? 17 : 16)) & 1u;
-        } else if (uni) {
-            if (use) {  // (another generation: the rows now)
-#pragma unroll
-                for (int r = 0; r < ONCE_ROWS; r++) {
-                    const uint32_t g8 = 8u * (l + 64u * r);
-                    if (g8 < fill) st[r] = *reinterpret_cast<const uint4*>(pst + g8);
-                }
-            }
-            const uint32_t p = u ? 0x00010001u : 0u;
-            const uint32_t rl[4] = {p, p, p, p};
-#pragma unroll
-            for (int r = 0; r < ONCE_ROWS; r++) count_row(8u * (l + 64u * r), st[r], rl);
-            for (uint32_t r = ONCE_ROWS; 512u * r < fill; r++) {  // buckets of more than 4096 pod slots
-                const uint32_t g8 = 8u * (l + 64u * r);
-                const uint4 s4 = g8 < fill ? *reinterpret_cast<const uint4*>(pst + g8) : make_uint4(0, 0, 0, 0);
-                count_row(g8, s4, rl);
-            }
-        } else {
-            uint4 nd[ONCE_ROWS];
-#pragma unroll
-            for (int r = 0; r < ONCE_ROWS; r++) {
-                const uint32_t g8 = 8u * (l + 64u * r);
-                nd[r] = g8 < fill ? *reinterpret_cast<const uint4*>(pnd_ + g8) : make_uint4(0, 0, 0, 0);
-                if (use && g8 < fill) st[r] = *reinterpret_cast<const uint4*>(pst + g8);
-            }
-            __builtin_amdgcn_wave_barrier();  // (the wave's node flags are in LDS)
-#pragma unroll
-            for (int r = 0; r < ONCE_ROWS; r++) {
-                uint32_t rl[4];
-                lds_flags(nd[r], rl);
-                count_row(8u * (l + 64u * r), st[r], rl);
-            }
-            for (uint32_t r = ONCE_ROWS; 512u * r < fill; r++) {
-                const uint32_t g8 = 8u * (l + 64u * r);
-                uint4 s4 = make_uint4(0, 0, 0, 0), n4 = s4;
-                if (g8 < fill) {
-                    s4 = *reinterpret_cast<const uint4*>(pst + g8);
-                    n4 = *reinterpret_cast<const uint4*>(pnd_ + g8);
-                }
-                uint32_t rl[4];
-                lds_flags(n4, rl);
-                count_row(g8, s4, rl);
-            }
-        }
-        OSTAMP(2);
+        if (S.trace && t == 0) S.trace[(size_t)(S.n_chain + b) * TRACE_SLOTS + 6] = __builtin_amdgcn_s_memrealtime();
+        return;
     }
-    // ---- counts: wave -> block -> XCD shard -> fleet
-    auto wsum = [](uint32_t x) { return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(x), 63); };
+    const uint32_t bo = b - n_stream, n_once = gridDim.x - n_stream;
     {
-        const uint64_t v0 = wsum(hb) | wsum(lock) << ONCE_FIELD_BITS, v1 = wsum(mng) | wsum(rdy) << ONCE_FIELD_BITS;
-        const uint64_t v2 = wsum(ev) | wsum(tot) << ONCE_FIELD_BITS, v3 = wsum(pnd) | wsum(run) << ONCE_FIELD_BITS;
-        const uint64_t v4 = __ballot(rare != 0) ? 1u : 0u;
-        if (l == 0) part[w][0] = v0, part[w][1] = v1, part[w][2] = v2, part[w][3] = v3, part[w][4] = v4;
-        if constexpr (SUM == ONCE_SUM_BUILD) {  // the bucket's summary (one wave = one bucket)
-            const uint32_t E0 = (uint32_t)wsum(be0), E1 = (uint32_t)wsum(be1);
-            const uint32_t k0 = __ballot(br0 != 0) ? 1u : 0u, k1 = __ballot(br1 != 0) ? 1u : 0u;
-            if (l == 0 && bk < S.nb)
-                S.once_sum[bk] = make_uint4(E0 | E1 << 16, (uint32_t)(v2 >> ONCE_FIELD_BITS) | (uint32_t)(v3 & ONCE_M27) << 16,
-                                            (uint32_t)(v3 >> ONCE_FIELD_BITS) | k0 << 16 | k1 << 17, gen);
-        }
+#define ONCE_B bo
+#define ONCE_G n_once
+        constexpr bool ONCE_BODY = false;
+#include "once_count.inc"
+#undef ONCE_B
+#undef ONCE_G
     }
-    __syncthreads();
-    if (t < (uint32_t)ONCE_ACC_WORDS) {
-        uint64_t v = 0;
-#pragma unroll
-        for (int i = 0; i < ONCE_WAVES; i++) v += part[i][t];
-        const uint32_t G = gridDim.x, x = b & 7u, nsh = min(G, 8u), nx = (G - x + 7u) / 8u;
-        const unsigned long long old = atomicAdd(&S.bar->once_acc[x][t][0], (1ull << ACC_SHIFT) | v);
-        if ((old >> ACC_SHIFT) == nx - 1u) {  // the shard is complete
-            const uint64_t sx = (old & ACC_MASK) + v;
-            st_sc1(&S.bar->once_acc[x][t][0], 0ull);  // the next tick starts from zero
-            const unsigned long long o2 = atomicAdd(&S.bar->once_acc[8][t][0], (1ull << ACC_SHIFT) | sx);
-            if ((o2 >> ACC_SHIFT) == nsh - 1u) {
-                st_sc1(&S.bar->once_acc[8][t][0], 0ull);
-                once_publish(S, t, (o2 & ACC_MASK) + sx, n_hb, phases, __builtin_amdgcn_s_memrealtime());
-            }
-        }
+    // this block's slice of what stream_share leaves the counting blocks (block-uniform)
+    if (S.stream_share < 1024 && !(phases & TICK_NOSTREAM) && hb_share_any(S, hb_bodies(S, n_hb), bo, n_once)) {
+        build_hb_template<NT>(S, hb_tmpl, now_unix, start_unix);
+        hb_write_share<GEN_HB, NT>(S, hb_tmpl4, &hb_delta, prev_unix, hb_bodies(S, n_hb), false, bo, n_once);
     }
-    OSTAMP(3);
-    // ---- the one heartbeat body (hb_bodies), arena offset 0
-    if (b == 0 && n_hb) {
-        const Ts nw = format_ts(now_unix), sw = format_ts(start_unix);
-        const uint32_t nb16 = 16u * S.hb_units;
-        for (uint32_t i = t; i < nb16; i += 64u * ONCE_WAVES) {
-            const uint8_t k = S.hb_kind[i];
-            tmpl[i] = (uint8_t)(k == 0xFF ? S.hb_static[i] : k < TS_LEN ? ts_byte(nw, k) : ts_byte(sw, k - TS_LEN));
-        }
-        __syncthreads();
-        for (uint32_t i = t; i < S.hb_units; i += 64u * ONCE_WAVES)
-            reinterpret_cast<uint4*>(S.arena)[i] = reinterpret_cast<const uint4*>(tmpl)[i];
-    }
-    OSTAMP(6);
-#undef OSTAMP
 }
 
 uint32_t once_blocks(const DevState& S) { return (S.nb + ONCE_WAVES - 1) / ONCE_WAVES; }
@@ -2936,6 +2806,27 @@ void launch_tick_once(const DevState& S, uint64_t now, uint64_t start, uint32_t 
     if (t0)
         hipExtLaunchKernelGGL(kern, dim3(grid), dim3(64 * ONCE_WAVES), 0, st, t0, t1, 0, S, now, start, n_hb, phases, gen);
     else hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * ONCE_WAVES), 0, st, S, now, start, n_hb, phases, gen);
+}
+
+template <bool GEN_HB>
+static decltype(&k_once_stream<false, ONCE_SUM_OFF, false>) once_stream_kernel(bool cni, uint32_t sum_mode) {
+    if (sum_mode == ONCE_SUM_BUILD)
+        return cni ? k_once_stream<true, ONCE_SUM_BUILD, GEN_HB> : k_once_stream<false, ONCE_SUM_BUILD, GEN_HB>;
+    if (sum_mode == ONCE_SUM_USE) return cni ? k_once_stream<true, ONCE_SUM_USE, GEN_HB> : k_once_stream<false, ONCE_SUM_USE, GEN_HB>;
+    return cni ? k_once_stream<true, ONCE_SUM_OFF, GEN_HB> : k_once_stream<false, ONCE_SUM_OFF, GEN_HB>;
+}
+
+void launch_tick_once_stream(const DevState& S, uint32_t n_stream, uint64_t now, uint64_t start, uint32_t n_hb, int phases,
+                             uint32_t sum_mode, uint32_t gen, uint64_t hb_prev, hipStream_t st, hipEvent_t t0, hipEvent_t t1) {
+    const uint32_t grid = n_stream + once_blocks(S);
+    auto kern = S.hb_units == (uint32_t)HB_CHUNKS ? once_stream_kernel<false>(S.cni != 0, sum_mode)
+                                                  : once_stream_kernel<true>(S.cni != 0, sum_mode);
+    if (t0)
+        hipExtLaunchKernelGGL(kern, dim3(grid), dim3(64 * ONCE_WAVES), 0, st, t0, t1, 0, S, now, start, n_hb, phases, gen,
+                              hb_prev, n_stream);
+    else
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * ONCE_WAVES), 0, st, S, now, start, n_hb, phases, gen, hb_prev,
+                           n_stream);
 }
 
 // ---------------------------------------------------------------------------

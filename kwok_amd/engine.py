@@ -632,7 +632,8 @@ class Engine(EngineBase):
     def read_wait(self):
         self._check(self._lib.kwok_read_wait(self._h), "read_wait")
 
-    STATS = ("ticks_full", "ticks_once", "once_redo", "once_summary", "ticks_hb_delta")  # KWOK_STAT_* order
+    STATS = ("ticks_full", "ticks_once", "once_redo", "once_summary", "ticks_hb_delta",
+             "ticks_once_stream")  # KWOK_STAT_* order
 
     def stats(self):
         """kwok_engine_stats: ticks run by k_tick / completed by k_once / k_once ticks redone / k_once
