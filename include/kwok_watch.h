@@ -101,6 +101,75 @@ enum {
 };
 int kwok_watch_stats(kwok_engine* e, uint64_t out[KWOK_WATCH_STAT_COUNT]);
 
+/* ---- List responses ---------------------------------------------
+ *
+ * A List body is one JSON value,
+ *   {"kind":"PodList","apiVersion":"v1","metadata":{"resourceVersion":"..","continue":".."},"items":[{..},{..}]}
+ * with no newline between its items.  The list framer gives one kwok_watch_frame
+ * per item (type KWOK_WATCH_ADDED, doc_off / doc_len the item's span with its
+ * braces, line_off == doc_off, the four metadata spans and KWOK_FRAME_ESC_* flags
+ * exactly as the watch framer fills them for an `object`) and the envelope's
+ * kwok_list_info.
+ *
+ * Rules (the same on host and device, frame for frame):
+ *   - grammar: the body is one JSON object in the codec's grammar (depth <= 64
+ *     counted from the root, lenient numbers, surrogate pairs), whitespace around it
+ *     allowed; the first occurrence of a key wins at every level;
+ *   - validity: a List decodes or it does not.  A body that is not a complete,
+ *     valid JSON object - a truncated one included - or whose `items` is present and
+ *     neither null nor an array of objects: KWOK_EINVAL for the call, *n_frames = 0,
+ *     no frame written, no stream left resident.  Nothing is consumed in part;
+ *   - `items` absent, null or []: zero frames, KWOK_OK.  `kind` is reported, not
+ *     judged: sending a PodList to the pod ingest is the caller's decision;
+ *   - guards: cap below the item count: KWOK_EINVAL with *n_frames set;
+ *     len > 0xFFFFFFF0: KWOK_EINVAL before any byte is read;
+ *   - an item without `metadata`, or with non-string members: empty spans, status OK;
+ *   - escapes: a routed key (the root's items / metadata / kind, the root
+ *     metadata's resourceVersion / continue, an item's metadata and its uid /
+ *     resourceVersion / name / namespace) holding an escape is compared as decoded
+ *     text, never guessed.  The device lists such an item for the host (*n_host),
+ *     which frames it from the caller's bytes; a body whose envelope the device does
+ *     not decide (no single array directly under the root that the envelope
+ *     confirms as the first `items`) is framed whole by the host framer
+ *     (KWOK_LIST_STAT_HOST_BODIES).
+ *   - info: the spans of the root's kind, metadata.resourceVersion and
+ *     metadata.continue, inside their quotes (empty when the value is absent, empty
+ *     or not a string; KWOK_LIST_ESC_* set when the raw text holds an escape), and
+ *     the span of the `items` array, brackets included (empty unless an array). */
+enum { KWOK_LIST_ESC_KIND = 1, KWOK_LIST_ESC_RV = 2, KWOK_LIST_ESC_CONTINUE = 4 };
+
+typedef struct kwok_list_info {
+    kwok_str kind, resource_version, continue_; /* inside the quotes; offsets into the body */
+    kwok_str items;                             /* the items array, brackets included */
+    uint32_t flags;                             /* KWOK_LIST_ESC_* */
+    uint32_t reserved0;
+} kwok_list_info;
+
+/* Host framer, the yardstick.  frames[cap]; *n_frames = the item count.  Returns
+ * KWOK_OK or KWOK_EINVAL (rules above). */
+int kwok_frame_list(const char* body, size_t len, kwok_watch_frame* frames, size_t cap, size_t* n_frames,
+                    kwok_list_info* info);
+
+/* GPU framer: uploads the body once, frames it there and copies the frames back.
+ * The body stays resident as THE stream under *stream_id (it replaces a watch
+ * stream, as every framing call does); kwok_ingest_pods_framed /
+ * kwok_ingest_nodes_framed then run on it unchanged (ADDED: KWOK_OP_UPSERT).
+ * *n_host: the items the host framed.  The caller's buffer must stay valid and
+ * unchanged until the next framing call or kwok_engine_destroy.  Return value and
+ * errors as kwok_frame_list; a failed call leaves no stream resident. */
+int kwok_frame_list_gpu(kwok_engine* e, const char* body, size_t len, kwok_watch_frame* frames, size_t cap,
+                        size_t* n_frames, kwok_list_info* info, size_t* n_host, uint64_t* stream_id);
+
+enum {
+    KWOK_LIST_STAT_BODIES = 0,   /* bodies given to kwok_frame_list_gpu (past its argument checks) */
+    KWOK_LIST_STAT_ITEMS,        /* items framed */
+    KWOK_LIST_STAT_HOST_ITEMS,   /* ... of them framed by the host (an escaped routed key) */
+    KWOK_LIST_STAT_HOST_BODIES,  /* bodies handed whole to the host framer */
+    KWOK_LIST_STAT_BYTES,        /* body bytes uploaded */
+    KWOK_LIST_STAT_COUNT
+};
+int kwok_list_stats(kwok_engine* e, uint64_t out[KWOK_LIST_STAT_COUNT]);
+
 #ifdef __cplusplus
 }
 #endif

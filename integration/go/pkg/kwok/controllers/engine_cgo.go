@@ -16,10 +16,12 @@ package controllers
 #cgo LDFLAGS: -L${SRCDIR}/../../../third_party/kwok_amd/lib -lkwok_engine -Wl,-rpath,${SRCDIR}/../../../third_party/kwok_amd/lib
 #include <stdlib.h>
 #include "kwok_engine.h"
+#include "kwok_watch.h"
 */
 import "C"
 
 import (
+	"bytes"
 	"encoding/binary"
 	"fmt"
 	"net"
@@ -510,6 +512,69 @@ func (g *gpuEngine) ingestNodesJSON(codec *gpuCodec, arena []byte, offs []uint64
 	copy(handles, res[:n])
 	copy(status, res[n:2*n])
 	nHost = int(nh)
+	return
+}
+
+// listFrame: one item of a List body (kwok_watch_frame, type ADDED): the spans are
+// offsets into the body
+type listFrame = C.kwok_watch_frame
+
+// frameList: kwok_frame_list_gpu - one complete List response body framed on the
+// GPU: one frame per item, the envelope's kind / resourceVersion / continue.  The
+// body is staged in page-locked memory and stays resident as the engine's stream
+// under streamID until the next framing call; ingestNodesFramed /
+// ingestPodsFramed decode its items in place.  A body that is no valid list is an
+// error (nothing stays resident).
+func (g *gpuEngine) frameList(body []byte) (frames []listFrame, info C.kwok_list_info, staged []byte, streamID uint64, err error) {
+	arp, err := g.arBuf.get(len(body) + 1)
+	if err != nil {
+		return
+	}
+	staged = unsafe.Slice((*byte)(arp), len(body)+1)[:len(body)]
+	copy(staged, body)
+	capN := bytes.Count(body, []byte("{")) // a bound on the item count
+	frames = make([]listFrame, capN+1)
+	var nf, nh C.size_t
+	var sid C.uint64_t
+	rc := C.kwok_frame_list_gpu(g.h, (*C.char)(arp), C.size_t(len(body)), &frames[0], C.size_t(capN), &nf, &info, &nh, &sid)
+	if rc < 0 {
+		err = fmt.Errorf("kwok_frame_list_gpu: %d: %s", int(rc), g.lastError())
+		return
+	}
+	return frames[:int(nf)], info, staged, uint64(sid), nil
+}
+
+// ingestNodesFramed / ingestPodsFramed: kwok_ingest_nodes_framed /
+// kwok_ingest_pods_framed over frames idx of the resident stream (a List body's
+// items are upserts); no document byte is uploaded again
+func (g *gpuEngine) ingestNodesFramed(codec *gpuCodec, streamID uint64, idx []uint32) (handles, status []int32, err error) {
+	n := len(idx)
+	handles, status = make([]int32, n), make([]int32, n)
+	if n == 0 {
+		return
+	}
+	var nh C.size_t
+	rc := C.kwok_ingest_nodes_framed(g.h, codec.c, C.uint64_t(streamID), (*C.uint32_t)(&idx[0]), C.size_t(n),
+		(*C.int32_t)(&handles[0]), (*C.int32_t)(&status[0]), &nh)
+	if rc < 0 {
+		err = fmt.Errorf("kwok_ingest_nodes_framed: %d: %s", int(rc), g.lastError())
+	}
+	return
+}
+
+func (g *gpuEngine) ingestPodsFramed(codec *gpuCodec, streamID uint64, idx []uint32, in []int32) (handles, status []int32, err error) {
+	n := len(idx)
+	handles, status = make([]int32, n), make([]int32, n)
+	if n == 0 {
+		return
+	}
+	released := make([]uint32, n)
+	var nh C.size_t
+	rc := C.kwok_ingest_pods_framed(g.h, codec.c, C.uint64_t(streamID), (*C.uint32_t)(&idx[0]), (*C.int32_t)(&in[0]),
+		C.size_t(n), (*C.int32_t)(&handles[0]), (*C.int32_t)(&status[0]), (*C.uint32_t)(&released[0]), &nh)
+	if rc < 0 {
+		err = fmt.Errorf("kwok_ingest_pods_framed: %d: %s", int(rc), g.lastError())
+	}
 	return
 }
 

@@ -16,6 +16,7 @@ package controllers
 
 /*
 #include "kwok_engine.h"
+#include "kwok_watch.h"
 */
 import "C"
 
@@ -36,6 +37,7 @@ import (
 	metav1 "k8s.io/apimachinery/pkg/apis/meta/v1"
 	"k8s.io/apimachinery/pkg/types"
 	"k8s.io/apimachinery/pkg/watch"
+	"k8s.io/client-go/kubernetes/scheme"
 
 	"sigs.k8s.io/kwok/pkg/cni"
 	"sigs.k8s.io/kwok/pkg/log"
@@ -220,6 +222,22 @@ func newGPUController(conf Config, interval time.Duration) (*GPUController, erro
 func (c *GPUController) Start(ctx context.Context) error {
 	nodeOpt := metav1.ListOptions{LabelSelector: c.conf.ManageNodesWithLabelSelector}
 	podOpt := metav1.ListOptions{FieldSelector: podFieldSelector}
+	// KWOK_GPU_LIST=1: what exists is listed in pages first (ListNodes / ListPods at
+	// Start, node_controller.go:282-296, pod_controller.go:357-368), each page framed
+	// on the GPU and ingested in place; the watches then open from the lists'
+	// resourceVersion.  Otherwise the watches open without one and the apiserver
+	// replays every object as an Added event - unpaged, and not served for 10M pods.
+	if os.Getenv("KWOK_GPU_LIST") == "1" {
+		rv, err := c.listInto(ctx, true, nodeOpt)
+		if err != nil {
+			return fmt.Errorf("failed to list nodes: %w", err)
+		}
+		nodeOpt.ResourceVersion = rv
+		if rv, err = c.listInto(ctx, false, podOpt); err != nil {
+			return fmt.Errorf("failed to list pods: %w", err)
+		}
+		podOpt.ResourceVersion = rv
+	}
 	if err := c.watch(ctx, true, nodeOpt); err != nil {
 		return fmt.Errorf("failed to watch nodes: %w", err)
 	}
@@ -228,6 +246,100 @@ func (c *GPUController) Start(ctx context.Context) error {
 	}
 	go c.loop(ctx)
 	return nil
+}
+
+// listPageSize: the pager's default (client-go tools/pager: 500)
+const listPageSize = 500
+
+// listInto pages through the kind's List with Limit and Continue, taking each
+// page's raw body (DoRaw: no typed decode), frames it on the GPU
+// (kwok_frame_list_gpu) and ingests its items from the resident body as upserts
+// (kwok_ingest_nodes_framed / kwok_ingest_pods_framed).  It runs before the tick
+// loop starts, so it owns the engine.  Returns the list's resourceVersion for
+// the watch.  Objects absent from the list are not deleted.
+func (c *GPUController) listInto(ctx context.Context, nodes bool, opt metav1.ListOptions) (string, error) {
+	resource := "pods"
+	if nodes {
+		resource = "nodes"
+	}
+	opt.Limit = listPageSize
+	text := func(body []byte, s C.kwok_str, escaped bool) (string, error) {
+		raw := body[s.off : s.off+s.len]
+		if !escaped {
+			return string(raw), nil
+		}
+		var out string
+		err := json.Unmarshal(append(append([]byte{'"'}, raw...), '"'), &out)
+		return out, err
+	}
+	rv := ""
+	for {
+		body, err := c.conf.ClientSet.CoreV1().RESTClient().Get().Resource(resource).
+			VersionedParams(&opt, scheme.ParameterCodec).DoRaw(ctx)
+		if err != nil {
+			return "", err
+		}
+		frames, info, staged, sid, err := c.eng.frameList(body)
+		if err != nil {
+			return "", err
+		}
+		idx, hs := make([]uint32, 0, len(frames)), make([]int32, 0, len(frames))
+		for i := range frames {
+			f := &frames[i]
+			h := int32(-1)
+			if !nodes {
+				uid, err := text(staged, f.uid, f.flags&C.KWOK_FRAME_ESC_UID != 0)
+				if err != nil {
+					return "", err
+				}
+				if known, ok := c.podByUID[types.UID(uid)]; ok {
+					h = known
+				}
+			}
+			idx, hs = append(idx, uint32(i)), append(hs, h)
+		}
+		var out, ss []int32
+		if nodes {
+			out, ss, err = c.eng.ingestNodesFramed(c.codec, sid, idx)
+		} else {
+			out, ss, err = c.eng.ingestPodsFramed(c.codec, sid, idx, hs)
+		}
+		if err != nil {
+			return "", err
+		}
+		for k, i := range idx {
+			if ss[k] != C.KWOK_OK {
+				continue // outside the engine's domain (DESIGN.md §2)
+			}
+			f := &frames[i]
+			name, err := text(staged, f.name, f.flags&C.KWOK_FRAME_ESC_NAME != 0)
+			if err != nil {
+				return "", err
+			}
+			if nodes {
+				c.nodeName[out[k]] = name
+				c.nodeHandle[name] = out[k]
+				continue
+			}
+			ns, err := text(staged, f.namespace_, f.flags&C.KWOK_FRAME_ESC_NS != 0)
+			if err != nil {
+				return "", err
+			}
+			uid, _ := text(staged, f.uid, f.flags&C.KWOK_FRAME_ESC_UID != 0)
+			c.podByUID[types.UID(uid)] = out[k]
+			c.podUID[out[k]] = types.UID(uid)
+			c.podRef[out[k]] = types.NamespacedName{Namespace: ns, Name: name}
+		}
+		if rv, err = text(staged, info.resource_version, info.flags&C.KWOK_LIST_ESC_RV != 0); err != nil {
+			return "", err
+		}
+		if opt.Continue, err = text(staged, info.continue_, info.flags&C.KWOK_LIST_ESC_CONTINUE != 0); err != nil {
+			return "", err
+		}
+		if opt.Continue == "" {
+			return rv, nil
+		}
+	}
 }
 
 // watch from the current state (a watch without resourceVersion first sends an

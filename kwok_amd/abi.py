@@ -112,6 +112,16 @@ class WatchFrame(C.Structure):
                 ("uid", KwokStr), ("resource_version", KwokStr), ("name", KwokStr), ("namespace_", KwokStr)]
 
 
+LIST_ESC_KIND, LIST_ESC_RV, LIST_ESC_CONTINUE = 1, 2, 4
+LIST_STATS = ("bodies", "items", "host_items", "host_bodies", "body_bytes")  # KWOK_LIST_STAT_* order
+
+
+class ListInfo(C.Structure):
+    """kwok_list_info: the envelope of a List body (offsets into the body)"""
+    _fields_ = [("kind", KwokStr), ("resource_version", KwokStr), ("continue_", KwokStr), ("items", KwokStr),
+                ("flags", C.c_uint32), ("reserved0", C.c_uint32)]
+
+
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 
@@ -171,6 +181,7 @@ POD_EVENT_DTYPE = _np_dtype(PodEvent)
 POD_REC_DTYPE = _np_dtype(PodRec)
 POD_REC12_DTYPE = _np_dtype(PodRec12)
 WATCH_FRAME_DTYPE = _np_dtype(WatchFrame)
+LIST_INFO_DTYPE = _np_dtype(ListInfo)
 
 
 def ip4(s: str) -> int:

@@ -50,6 +50,32 @@ def frame_watch(data, cap=None):
     return frames[:nf.value], used.value
 
 
+def frame_list(body, cap=None):
+    """kwok_frame_list, the host framer of a List body (include/kwok_watch.h): one
+    complete response body -> (frames (WATCH_FRAME_DTYPE), info (abi.ListInfo)).  cap:
+    the frames array's size (default: a bound on the item count); KwokError(EINVAL)
+    when it is smaller, with .n_frames set, and when the body is no valid list."""
+    import numpy as np
+    lib = load_engine_lib()
+    body = bytes(body)
+    if cap is None:
+        cap = body.count(b"{")
+    frames = np.zeros(max(cap, 1), abi.WATCH_FRAME_DTYPE)
+    nf, info = C.c_size_t(), abi.ListInfo()
+    rc = lib.kwok_frame_list(body or b"\0", len(body), frames.ctypes.data, cap, C.byref(nf), C.byref(info))
+    if rc < 0:
+        err = KwokError(rc, "frame_list: %s" % lib.kwok_codec_last_error().decode())
+        err.n_frames = nf.value
+        raise err
+    return frames[:nf.value], info
+
+
+def list_text(body, span, escaped=False):
+    """the text of one of a ListInfo's string spans (decoded when its KWOK_LIST_ESC_* bit is set)"""
+    raw = bytes(body[span.off:span.off + span.len])
+    return json.loads(b'"' + raw + b'"') if escaped else raw.decode()
+
+
 class Batch:
     """Decoded records of one ingest batch plus their shared arena."""
 

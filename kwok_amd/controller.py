@@ -53,6 +53,12 @@ Per tick (step):
 The backend is the HIP engine; tests may pass another implementation of the
 same ABI (the CPU oracle) as the checker.
 
+feed_list takes one complete page of a List response (the reference's ListNodes /
+ListPods at Start): at step each kind's pages are framed on the GPU
+(kwok_frame_list_gpu, include/kwok_watch.h) and their items ingested as upserts
+from the resident body, before that kind's events; list_cursor[kind] then holds the
+page's resourceVersion and continue token.
+
 feed_watch is the same controller fed with the raw bytes of the watch responses
 (a rest.Request.Stream read loop instead of the typed watcher): step 1-3 then
 run on frames (include/kwok_watch.h) - the stream of each kind is framed on the
@@ -70,8 +76,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import abi
-from .codec import Codec
-from .engine import Engine, make_config
+from .codec import Codec, list_text
+from .engine import Engine, KwokError, make_config
 
 READ_CHUNK = 64 << 20  # engine_cgo.go readChunk
 
@@ -280,6 +286,9 @@ class Stats:
     watch_host_frames: int = 0  # ... of them by the host framer (an escaped type or routed key)
     watch_bad_frames: int = 0   # frames whose status is not OK (malformed lines, unknown types): skipped
     watch_skipped: int = 0      # BOOKMARK / ERROR frames: skipped
+    list_items: int = 0         # feed_list: items framed
+    list_host_items: int = 0    # ... of them by the host framer (an escaped routed key)
+    list_bad_bodies: int = 0    # pages that are no valid list: dropped whole
     bodies: int = 0
     rejected: list = field(default_factory=list)
 
@@ -338,6 +347,8 @@ class Controller:
         self.reenter = []     # objects of pod patches without a podIP (step 6)
         self.raw = {True: bytearray(), False: bytearray()}  # feed_watch: raw watch bytes per kind (nodes: True)
         self.fed = set()      # the kinds fed raw bytes since the last step
+        self.pages = {True: [], False: []}  # feed_list: complete List bodies per kind, in feed order
+        self.list_cursor = {}  # "nodes" / "pods" -> kind, resource_version, continue_ of the kind's last page (decoded text)
 
     def close(self):
         self.eng.close()
@@ -360,6 +371,18 @@ class Controller:
             raise ValueError("feed_watch after on_event for the same kind within one step")
         self.fed.add(bool(nodes))
         self.raw[bool(nodes)] += data
+
+    def feed_list(self, nodes: bool, body: bytes):
+        """one complete page of the node (nodes=True) or pod List response
+        (pod_controller.go:357-368, node_controller.go:282-296): framed and ingested
+        at the next step, before the kind's watch bytes and typed events; its items
+        are upserts (objects absent from a list are not deleted).  After the step
+        list_cursor[kind] holds the page's resourceVersion and continue token: the
+        caller requests the next page with the token, or opens its watch from the
+        version."""
+        if not hasattr(self.eng, "frame_list"):
+            raise ValueError("feed_list needs the engine backend (kwok_frame_list_gpu)")
+        self.pages[bool(nodes)].append(bytes(body))
 
     def on_event(self, nodes: bool, typ: str, obj: dict):
         if bool(nodes) in self.fed:
@@ -391,9 +414,14 @@ class Controller:
         fed, self.fed = self.fed, set()
         nb = self._encode(nw)
         pb = self._encode(pw)
+        pages, self.pages = self.pages, {True: [], False: []}
+        for body in pages[True]:  # a kind's list pages go first, in feed order: the watch starts at their version
+            self._flush_list(True, body)
         self._flush_nodes(nb)
         if True in fed:
             self._flush_watch(True)
+        for body in pages[False]:
+            self._flush_list(False, body)
         self._flush_pods(pb)
         if False in fed:
             self._flush_watch(False)
@@ -570,16 +598,41 @@ class Controller:
                 self.pod_ref[h] = (md.get("namespace", ""), md.get("name", ""))
 
     def _flush_watch(self, nodes):
-        """step 1-3 over the raw bytes of one kind's watch: framed on the GPU, echoes
-        dropped by the frames' (uid, resourceVersion) under _encode's rule, the kept
-        frames ingested from the resident stream; names for the patches from the
+        """the raw bytes of one kind's watch: framed on the GPU, then _ingest_frames:
+        echoes dropped by the frames' (uid, resourceVersion) under _encode's rule, the
+        kept frames ingested from the resident stream; names for the patches from the
         frames' spans.  The unconsumed tail stays buffered."""
         stream = bytes(self.raw[nodes])
         frames, used, n_host, sid = self.eng.frame_watch(stream)
         self.raw[nodes] = bytearray(stream[used:])
         self.stats.watch_frames += len(frames)
         self.stats.watch_host_frames += n_host
+        self._ingest_frames(nodes, stream, frames, sid)
 
+    def _flush_list(self, nodes, body):
+        """one List page: framed on the GPU, its items taken as upserts by the path
+        of the watch frames (an item whose (uid, resourceVersion) is an echo of the
+        engine's own patch is dropped); the page's resourceVersion and continue
+        token go to list_cursor.  A body that is no valid list is counted and
+        dropped (client-go: the List call fails, the caller lists again)."""
+        try:
+            frames, info, n_host, sid = self.eng.frame_list(body)
+        except KwokError as err:
+            if err.code != abi.EINVAL:
+                raise
+            self.stats.list_bad_bodies += 1
+            return
+        self.stats.list_items += len(frames)
+        self.stats.list_host_items += n_host
+        self.list_cursor["nodes" if nodes else "pods"] = dict(
+            kind=list_text(body, info.kind, info.flags & abi.LIST_ESC_KIND),
+            resource_version=list_text(body, info.resource_version, info.flags & abi.LIST_ESC_RV),
+            continue_=list_text(body, info.continue_, info.flags & abi.LIST_ESC_CONTINUE))
+        self._ingest_frames(nodes, body, frames, sid)
+
+    def _ingest_frames(self, nodes, stream, frames, sid):
+        """step 1-3 over the frames of the resident stream (a watch stream's lines or
+        a List body's items)"""
         def text(f, key, bit):
             raw = stream[int(f[key]["off"]):int(f[key]["off"]) + int(f[key]["len"])]
             return json.loads(b'"' + raw + b'"') if f["flags"] & bit else raw.decode()

@@ -927,3 +927,109 @@ extern "C" int kwok_frame_watch(const char* stream, size_t len, kwok_watch_frame
     }
     return bad;
 }
+
+// ---------------------------------------------------------------- list frames
+// kwok_frame_list (kwok_watch.h): the host framer of a List body, the yardstick of
+// the device framer (json.hip k_list_*) and the decider of what that one lists.
+// client-go decodes the whole body into a typed list (pod_controller.go:357-368,
+// node_controller.go:282-296); here every item's span and the four metadata
+// strings are kept, and the envelope's kind, resourceVersion and continue token.
+namespace {
+// one item's frame from its parsed object
+void item_frame(const JV& ob, kwok_watch_frame* f) {
+    memset(f, 0, sizeof *f);
+    f->type = KWOK_WATCH_ADDED;
+    f->status = KWOK_OK;
+    f->line_off = f->doc_off = ob.off;
+    f->doc_len = ob.len;
+    const JV* md = ob.get("metadata");
+    if (!md || md->t != JV::OBJ) return;
+    const char* keys[4] = {"uid", "resourceVersion", "name", "namespace"};
+    kwok_str* outs[4] = {&f->uid, &f->resource_version, &f->name, &f->namespace_};
+    for (int q = 0; q < 4; q++) {
+        const JV* v = md->get(keys[q]);
+        if (!v || v->t != JV::STR) continue;  // a non-string value: an empty span
+        if (v->len) *outs[q] = kwok_str{v->off, v->len};
+        if (v->escaped) f->flags |= (uint8_t)(1u << q);  // KWOK_FRAME_ESC_*: the span is the raw text
+    }
+}
+// the envelope's strings; shift: what the offsets past `from` gain (list_envelope's emptied array)
+void list_info(const JV& root, kwok_list_info* info, uint32_t from, uint32_t shift) {
+    memset(info, 0, sizeof *info);
+    auto put = [&](const JV* v, kwok_str* out, uint32_t bit) {
+        if (!v || v->t != JV::STR) return;
+        if (v->len) *out = kwok_str{v->off > from ? v->off + shift : v->off, v->len};
+        if (v->escaped) info->flags |= bit;
+    };
+    put(root.get("kind"), &info->kind, KWOK_LIST_ESC_KIND);
+    const JV* md = root.get("metadata");
+    if (md && md->t == JV::OBJ) {
+        put(md->get("resourceVersion"), &info->resource_version, KWOK_LIST_ESC_RV);
+        put(md->get("continue"), &info->continue_, KWOK_LIST_ESC_CONTINUE);
+    }
+}
+}  // namespace
+
+bool kwok::frame_item(const char* body, uint32_t lo, uint32_t hi, kwok_watch_frame* f) {
+    std::deque<std::string> store;
+    JV ob;
+    Parser ps(body, lo, hi - lo, &store);
+    if (!ps.value(ob, 2) || ob.t != JV::OBJ || ps.i != ps.n || ob.off != lo) return false;
+    item_frame(ob, f);
+    return true;
+}
+
+int kwok::list_envelope(const char* body, size_t len, uint32_t open, uint32_t close, kwok_list_info* info) {
+    if (open >= close || close >= len) return KWOK_EINVAL;
+    std::string env(body, (size_t)open + 1);
+    env.append(body + close, len - close);
+    std::deque<std::string> store;
+    JV root;
+    Parser ps(env.data(), 0, env.size(), &store);
+    if (!ps.document(root) || root.t != JV::OBJ) return KWOK_EINVAL;
+    const JV* items = root.get("items");
+    if (!items || items->t != JV::ARR || items->off != open) return 1;
+    {  // the key is confirmed by its raw bytes; an escaped spelling of it is the host framer's to decide
+        size_t k = open;
+        auto back_ws = [&]() {
+            while (k > 0 && (body[k - 1] == ' ' || body[k - 1] == '\t' || body[k - 1] == '\n' || body[k - 1] == '\r')) k--;
+        };
+        back_ws();
+        if (k == 0 || body[k - 1] != ':') return 1;
+        k--;
+        back_ws();
+        if (k < 7 || memcmp(body + k - 7, "\"items\"", 7)) return 1;
+    }
+    list_info(root, info, open, close - open - 1);
+    info->items = kwok_str{open, close - open + 1};
+    return KWOK_OK;
+}
+
+extern "C" int kwok_frame_list(const char* body, size_t len, kwok_watch_frame* frames, size_t cap, size_t* n_frames,
+                               kwok_list_info* info) {
+    static_assert(sizeof(kwok_list_info) == 40, "kwok_list_info is 40 bytes");
+    if (n_frames) *n_frames = 0;
+    if (info) memset(info, 0, sizeof *info);
+    if (!n_frames || !info || len > 0xFFFFFFF0ull || (len && !body) || (cap && !frames))
+        return fail(KWOK_EINVAL, "kwok_frame_list: null argument or body > 4 GiB");
+    std::deque<std::string> store;
+    JV root;
+    Parser ps(body, 0, len, &store);
+    if (!ps.document(root) || root.t != JV::OBJ) return fail(KWOK_EINVAL, "kwok_frame_list: the body is not a JSON object");
+    const JV* items = root.get("items");
+    if (items && items->t != JV::NUL) {
+        if (items->t != JV::ARR) return fail(KWOK_EINVAL, "kwok_frame_list: items is not an array");
+        for (const JV& it : items->a)
+            if (it.t != JV::OBJ) return fail(KWOK_EINVAL, "kwok_frame_list: an item is not an object");
+        if (items->a.size() > cap) {
+            *n_frames = items->a.size();
+            return fail(KWOK_EINVAL, "kwok_frame_list: cap smaller than the item count");
+        }
+    }
+    list_info(root, info, 0, 0);
+    if (!items || items->t != JV::ARR) return KWOK_OK;
+    info->items = kwok_str{items->off, items->len};
+    for (size_t i = 0; i < items->a.size(); i++) item_frame(items->a[i], &frames[i]);
+    *n_frames = items->a.size();
+    return KWOK_OK;
+}

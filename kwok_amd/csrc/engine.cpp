@@ -266,6 +266,15 @@ struct kwok_engine {
         std::vector<kwok_watch_frame> frames_h;
         uint64_t id = 0, next_id = 1;  // id 0: no stream resident
         uint64_t stats[KWOK_WATCH_STAT_COUNT] = {};
+        // the List body framer (json.hip k_list_*): eight arrays of per-tile words,
+        // the candidates' `{` offsets (their `}` go to ends), its counters
+        uint32_t* ltile = nullptr;     // [8][ltile_cap]
+        size_t ltile_cap = 0;
+        uint32_t* starts = nullptr;    // [scap]
+        size_t scap = 0;
+        uint32_t* lc = nullptr;        // device [KWOK_LIST_COUNTERS]
+        uint32_t* lc_h = nullptr;      // pinned [KWOK_LIST_COUNTERS]
+        uint64_t lstats[KWOK_LIST_STAT_COUNT] = {};
     } watch;
 
     // ---- the pod codec on the GPU (json.hip): per-document buffers, the codec's
@@ -1190,10 +1199,12 @@ void kwok_engine_destroy(kwok_engine* e) {
     }
     {
         auto& Wt = e->watch;
-        void* wp[] = {Wt.stream, Wt.tile_cnt, Wt.tile_base, Wt.ends, Wt.frames, Wt.host_list, Wt.counts};
+        void* wp[] = {Wt.stream, Wt.tile_cnt, Wt.tile_base, Wt.ends, Wt.frames, Wt.host_list, Wt.counts,
+                      Wt.ltile, Wt.starts, Wt.lc};
         for (void* p : wp)
             if (p) (void)hipFree(p);
         if (Wt.counts_h) (void)hipHostFree(Wt.counts_h);
+        if (Wt.lc_h) (void)hipHostFree(Wt.lc_h);
     }
     if (e->h_xall) (void)hipHostFree(e->h_xall);
     if (e->pinned) (void)hipHostFree(e->pinned);
@@ -3017,6 +3028,213 @@ int kwok_ingest_nodes_framed(kwok_engine* e, const kwok_codec* c, uint64_t strea
 int kwok_watch_stats(kwok_engine* e, uint64_t out[KWOK_WATCH_STAT_COUNT]) {
     if (!e || !out) return KWOK_EINVAL;
     for (int k = 0; k < KWOK_WATCH_STAT_COUNT; k++) out[k] = e->watch.stats[k];
+    return KWOK_OK;
+}
+
+// ---- List bodies (kwok_watch.h): split by bracket depth on the device, the items
+// parsed there, the envelope by the host from the caller's bytes ----
+namespace {
+static int list_reserve(kwok_engine* e, size_t tiles) {
+    auto& Wt = e->watch;
+    if (!Wt.lc) {
+        if (int rc = dalloc(e, &Wt.lc, (size_t)KWOK_LIST_COUNTERS)) return rc;
+        if (hipHostMalloc((void**)&Wt.lc_h, KWOK_LIST_COUNTERS * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
+            return e->fail(KWOK_ENOMEM, "list framer staging");
+    }
+    if (tiles > Wt.ltile_cap) {
+        if (Wt.ltile) (void)hipFree(Wt.ltile);
+        Wt.ltile = nullptr, Wt.ltile_cap = 0;
+        const size_t cap = std::max<size_t>(tiles + tiles / 4, 1024);
+        if (int rc = dalloc(e, &Wt.ltile, 8 * cap)) return rc;
+        Wt.ltile_cap = cap;
+    }
+    return KWOK_OK;
+}
+static int list_reserve_starts(kwok_engine* e, size_t n) {
+    auto& Wt = e->watch;
+    if (n <= Wt.scap) return KWOK_OK;
+    if (Wt.starts) (void)hipFree(Wt.starts);
+    Wt.starts = nullptr, Wt.scap = 0;
+    const size_t cap = std::max<size_t>(n + n / 4, 4096);
+    if (int rc = dalloc(e, &Wt.starts, cap)) return rc;
+    Wt.scap = cap;
+    return KWOK_OK;
+}
+}  // namespace
+
+int kwok_frame_list_gpu(kwok_engine* e, const char* body, size_t len, kwok_watch_frame* frames, size_t cap,
+                        size_t* n_frames, kwok_list_info* info, size_t* n_host, uint64_t* stream_id) {
+    if (n_frames) *n_frames = 0;
+    if (info) memset(info, 0, sizeof *info);
+    if (n_host) *n_host = 0;
+    if (stream_id) *stream_id = 0;
+    if (!e || !n_frames || !info || !stream_id || len > 0xFFFFFFF0ull || (len && !body) || (cap && !frames))
+        return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    auto& Wt = e->watch;
+    hipStream_t st = e->st;
+    Wt.id = 0;  // (a failed call leaves no stream resident)
+    Wt.frames_h.clear();
+    Wt.lstats[KWOK_LIST_STAT_BODIES]++;
+    if (!len) return e->fail(KWOK_EINVAL, "kwok_frame_list_gpu: an empty body");
+    const uint32_t tiles = (uint32_t)((len + KWOK_WATCH_TILE_BYTES - 1) / KWOK_WATCH_TILE_BYTES);
+    int rc = 0;
+    if ((rc = watch_reserve(e, len)) || (rc = list_reserve(e, tiles))) return rc;
+    const size_t padded = ((len + 15) & ~(size_t)15) + 16;
+    const size_t L = Wt.ltile_cap;
+    uint32_t *tq = Wt.ltile, *td0 = tq + L, *td1 = td0 + L, *qb = td1 + L, *db = qb + L, *ts = db + L, *te = ts + L;
+    uint32_t *lc = Wt.lc, *lh = Wt.lc_h;
+    // KWOK_INGEST_PROF: device-side stamps - upload | quotes + scans | count + scans | emit + range | parse
+    hipEvent_t pe[7] = {};
+    const auto t0 = clk::now();
+    if (e->iprof)
+        for (auto& x : pe) (void)hipEventCreate(&x);
+    auto stamp = [&](int k) {
+        if (pe[k]) (void)hipEventRecord(pe[k], st);
+    };
+    struct PeFree {
+        hipEvent_t* p;
+        ~PeFree() {
+            for (int k = 0; k < 7; k++)
+                if (p[k]) (void)hipEventDestroy(p[k]);
+        }
+    } pe_free{pe};
+    const bool prof = pe[0] != nullptr;
+    float ms[4] = {0, 0, 0, 0};  // quotes, count, emit, parse
+    uint32_t n = 0, nh = 0;
+    auto report = [&](const char* how) {
+        if (!prof) return;
+        fprintf(stderr, "[kwok list] %zu bytes, %u items (%u by the host), %s: k_list_quotes + scans %.3f ms, "
+                        "k_list_split<count> + scans %.3f ms, k_list_split<emit> + k_list_range %.3f ms, k_list_parse %.3f ms; "
+                        "the call %.2f ms\n", len, n, nh, how, ms[0], ms[1], ms[2], ms[3], ms_between(t0, clk::now()));
+    };
+    stamp(0);
+    HIPCHK(e, hipMemcpyAsync(Wt.stream, body, len, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemsetAsync(Wt.stream + len, 0, padded - len, st));
+    Wt.lstats[KWOK_LIST_STAT_BYTES] += len;
+    HIPCHK(e, hipMemsetAsync(lc, 0, KWOK_LIST_COUNTERS * sizeof(uint32_t), st));
+    HIPCHK(e, hipMemsetAsync(lc + LC_OPEN_POS, 0xFF, sizeof(uint32_t), st));
+    stamp(1);
+    launch_list_quotes(Wt.stream, len, tiles, tq, td0, td1, st);
+    launch_frame_scan(tq, tiles, qb, lc + LC_QUOTES, st);
+    launch_list_pick(qb, td0, td1, tiles, st);
+    launch_frame_scan(td0, tiles, db, lc + LC_DEPTH, st);
+    stamp(2);
+    launch_list_count(Wt.stream, len, tiles, qb, db, ts, te, lc, st);
+    launch_frame_scan(ts, tiles, ts, lc + LC_STARTS, st);
+    launch_frame_scan(te, tiles, te, lc + LC_ENDS, st);
+    HIPCHK(e, hipGetLastError());
+    stamp(3);
+    HIPCHK(e, hipMemcpyAsync(lh, lc, KWOK_LIST_COUNTERS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    if (prof) (void)hipEventElapsedTime(&ms[0], pe[1], pe[2]), (void)hipEventElapsedTime(&ms[1], pe[2], pe[3]);
+    // a valid body ends outside every string and every bracket, and an array that its
+    // root holds is closed once
+    if ((lh[LC_QUOTES] & 1u) || lh[LC_DEPTH] != 0 || lh[LC_STARTS] != lh[LC_ENDS] || lh[LC_OPEN_N] != lh[LC_CLOSE_N] ||
+        (lh[LC_OPEN_N] == 1 && lh[LC_OPEN_POS] >= lh[LC_CLOSE_POS])) {
+        report("unbalanced");
+        return e->fail(KWOK_EINVAL, "kwok_frame_list_gpu: the body is not a JSON object");
+    }
+    const uint32_t open = lh[LC_OPEN_POS], close = lh[LC_CLOSE_POS], S = lh[LC_STARTS];
+    int env = 1;
+    if (lh[LC_OPEN_N] == 1) {
+        // the device's part goes on while the host reads the envelope
+        if ((rc = watch_reserve_frames(e, S)) || (rc = list_reserve_starts(e, S))) return rc;
+        stamp(6);  // (the emit's start, after the host's wait for the counts)
+        launch_list_emit(Wt.stream, len, tiles, qb, db, ts, te, Wt.starts, Wt.ends, S, st);
+        launch_list_range(Wt.starts, S, open, close, lc, st);
+        HIPCHK(e, hipGetLastError());
+        stamp(4);
+        HIPCHK(e, hipMemcpyAsync(lh + LC_R0, lc + LC_R0, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        env = list_envelope(body, len, open, close, info);
+        HIPCHK(e, hipStreamSynchronize(st));
+        if (prof) (void)hipEventElapsedTime(&ms[2], pe[6], pe[4]);
+        if (env < 0) {
+            report("a bad envelope");
+            return e->fail(KWOK_EINVAL, "kwok_frame_list_gpu: the body is not a JSON object");
+        }
+    }
+    if (env == 1) {  // no single root array that is the first `items`: the host framer decides the whole body
+        Wt.lstats[KWOK_LIST_STAT_HOST_BODIES]++;
+        size_t nf = 0;
+        std::vector<kwok_watch_frame> tmp(cap);
+        rc = kwok_frame_list(body, len, tmp.data(), cap, &nf, info);
+        *n_frames = nf;
+        n = rc ? 0u : (uint32_t)nf;
+        report("the body framed by the host");
+        if (rc) return e->fail(KWOK_EINVAL, "kwok_frame_list_gpu: %s", kwok_codec_last_error());
+        if ((rc = watch_reserve_frames(e, nf))) return rc;
+        Wt.frames_h.assign(tmp.begin(), tmp.begin() + nf);
+        if (nf) {
+            HIPCHK(e, hipMemcpyAsync(Wt.frames, Wt.frames_h.data(), nf * sizeof(kwok_watch_frame), hipMemcpyHostToDevice, st));
+            HIPCHK(e, hipStreamSynchronize(st));
+            memcpy(frames, Wt.frames_h.data(), nf * sizeof(kwok_watch_frame));
+        }
+        Wt.lstats[KWOK_LIST_STAT_ITEMS] += nf;
+        Wt.len = len, Wt.host = body;
+        *stream_id = Wt.id = Wt.next_id++;
+        return KWOK_OK;
+    }
+    auto invalid = [&](const char* how) {
+        memset(info, 0, sizeof *info);
+        n = 0;
+        report(how);
+        return e->fail(KWOK_EINVAL, "kwok_frame_list_gpu: items is not an array of objects (%s)", how);
+    };
+    const uint32_t r0 = lh[LC_R0], r1 = lh[LC_R1];
+    if (r0 > r1 || r1 > S) return e->fail(KWOK_EDEVICE, "list framer: items %u..%u of %u candidates", r0, r1, S);
+    n = r1 - r0;
+    if (!n) {  // [ ]: only whitespace between the brackets
+        for (uint32_t p = open + 1; p < close; p++)
+            if (body[p] != ' ' && body[p] != '\t' && body[p] != '\n' && body[p] != '\r') return invalid("a stray byte");
+    }
+    // (the device's frames are sized by the candidates, not by cap: the body is judged first, as the host does)
+    launch_list_parse(Wt.stream, Wt.starts, Wt.ends, r0, n, open, close, Wt.frames, Wt.host_list, lc, st);
+    HIPCHK(e, hipGetLastError());
+    stamp(5);
+    Wt.frames_h.resize(n);
+    if (n) HIPCHK(e, hipMemcpyAsync(Wt.frames_h.data(), Wt.frames, (size_t)n * sizeof(kwok_watch_frame), hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipMemcpyAsync(lh + LC_BAD, lc + LC_BAD, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    if (prof && n) (void)hipEventElapsedTime(&ms[3], pe[4], pe[5]);
+    if (lh[LC_BAD]) {
+        Wt.frames_h.clear();
+        return invalid("an item or the text between items");
+    }
+    if (n > cap) {
+        memset(info, 0, sizeof *info);
+        Wt.frames_h.clear();
+        *n_frames = n;
+        return e->fail(KWOK_EINVAL, "kwok_frame_list_gpu: cap smaller than the item count (%u)", n);
+    }
+    nh = lh[LC_HOST];
+    if (nh) {  // the items the device listed: the host framer over the caller's bytes
+        std::vector<uint32_t> list(nh);
+        HIPCHK(e, hipMemcpyAsync(list.data(), Wt.host_list, (size_t)nh * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipStreamSynchronize(st));
+        for (uint32_t i : list) {
+            if (i >= n) return e->fail(KWOK_EDEVICE, "list framer: listed item %u of %u", i, n);
+            const uint32_t lo = Wt.frames_h[i].doc_off, hi = lo + Wt.frames_h[i].doc_len;
+            if (hi > len || !frame_item(body, lo, hi, &Wt.frames_h[i]))
+                return e->fail(KWOK_EDEVICE, "list framer: listed item %u does not parse on the host", i);
+            HIPCHK(e, hipMemcpyAsync(Wt.frames + i, &Wt.frames_h[i], sizeof(kwok_watch_frame), hipMemcpyHostToDevice, st));
+        }
+        HIPCHK(e, hipStreamSynchronize(st));
+    }
+    if (n) memcpy(frames, Wt.frames_h.data(), (size_t)n * sizeof(kwok_watch_frame));
+    *n_frames = n;
+    if (n_host) *n_host = nh;
+    Wt.len = len, Wt.host = body;
+    Wt.lstats[KWOK_LIST_STAT_ITEMS] += n;
+    Wt.lstats[KWOK_LIST_STAT_HOST_ITEMS] += nh;
+    *stream_id = Wt.id = Wt.next_id++;
+    report("split on the device");
+    return KWOK_OK;
+}
+
+int kwok_list_stats(kwok_engine* e, uint64_t out[KWOK_LIST_STAT_COUNT]) {
+    if (!e || !out) return KWOK_EINVAL;
+    for (int k = 0; k < KWOK_LIST_STAT_COUNT; k++) out[k] = e->watch.lstats[k];
     return KWOK_OK;
 }
 

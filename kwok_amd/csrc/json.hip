@@ -1641,4 +1641,378 @@ void launch_frame_parse(const uint8_t* s, const uint32_t* ends, uint32_t n, kwok
     const uint32_t bs = json_block(n);
     hipLaunchKernelGGL(k_frame_parse, dim3((n + bs - 1) / bs), dim3(bs), 0, st, s, ends, n, frames, host_list, n_host);
 }
+
+// ---------------------------------------------------------------------------
+// the List body framer (kwok_watch.h, kwok_frame_list_gpu): one JSON value,
+// {"kind":"PodList","metadata":{..},"items":[{..},{..}]}, no newline between items.
+// An item ends where the bracket depth returns to the array's, the depth needs the
+// in-string state, the state needs escaped quotes - scans that cross tiles:
+//   k_list_quotes  per 16-byte window the masks of unescaped quotes and of brackets;
+//                  per tile the count of unescaped quotes and the tile's net depth
+//                  change for both in-string states it may be entered in
+//   k_frame_scan   over the quote counts: a tile's entry state is its base's parity
+//   k_list_pick    the depth change of each tile's actual entry state;
+//   k_frame_scan   over those: a tile's entry depth (a wrapping 32-bit sum)
+//   k_list_split   <false> counts, per tile, the `{` that raise the depth 2 -> 3 and
+//                  the `}` that bring it back, and records the `[` / `]` that open and
+//                  close an array directly under the root; after two more scans <true>
+//                  writes their offsets at base + rank, in stream order
+//   k_list_range   the candidates inside the root array: a contiguous rank range
+//   k_list_parse   one thread per item: jparse (d0 = 2) over exactly the item's span,
+//                  and the gap before it (after the last one too): whitespace and,
+//                  between items, exactly one comma.  Any failure marks the body.
+// No kernel waits on another block: separate launches with scans between them.
+// Loads are guarded as nl_window's are.
+// ---------------------------------------------------------------------------
+namespace {
+// bit k set for each byte k of x equal to the byte repeated in pat (nl4's zero-byte test)
+__device__ __forceinline__ uint32_t eq4(uint32_t x, uint32_t pat) {
+    const uint32_t y = x ^ pat;
+    const uint32_t m = ~(((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y | 0x7F7F7F7Fu);
+    return (((m >> 7) & 0x01010101u) * 0x01020408u) >> 24;
+}
+__device__ __forceinline__ uint32_t eq16(const uint4& w, uint32_t pat) {
+    return eq4(w.x, pat) | eq4(w.y, pat) << 4 | eq4(w.z, pat) << 8 | eq4(w.w, pat) << 12;
+}
+// bit k set for each byte k of x whose bit 5 is set (`{` `}` have it, `[` `]` do not)
+__device__ __forceinline__ uint32_t bit5_4(uint32_t x) { return (((x >> 5) & 0x01010101u) * 0x01020408u) >> 24; }
+
+// one 16-byte window: its unescaped quotes, its opening and closing brackets of
+// both kinds (inside strings too), and which bytes are braces
+struct LWin {
+    uint32_t q, open, close, brace;
+};
+// A quote is escaped when the run of backslashes before it is odd.  The run may
+// begin in an earlier window: whether the byte before the window is a backslash
+// comes from the neighbour lane (lane 0: from memory), and only then does the lane
+// follow the run backwards through memory - bounded by the run, never before
+// offset 0.  Called by all lanes of the wave.
+__device__ __forceinline__ LWin list_window(const uint8_t* s, uint64_t off, uint64_t len, uint32_t lane) {
+    LWin r{0, 0, 0, 0};
+    uint32_t bs = 0;
+    const bool live = off < len;
+    if (live) {
+        const uint4 w = *reinterpret_cast<const uint4*>(s + off);
+        const uint32_t keep = len - off < 16 ? (1u << (uint32_t)(len - off)) - 1u : 0xFFFFu;
+        const uint4 v = make_uint4(w.x | 0x20202020u, w.y | 0x20202020u, w.z | 0x20202020u, w.w | 0x20202020u);
+        r.q = eq16(w, 0x22222222u) & keep;
+        bs = eq16(w, 0x5C5C5C5Cu) & keep;
+        r.open = eq16(v, 0x7B7B7B7Bu) & keep;   // `[` 5B | 20 = `{` 7B
+        r.close = eq16(v, 0x7D7D7D7Du) & keep;  // `]` 5D | 20 = `}` 7D
+        r.brace = bit5_4(w.x) | bit5_4(w.y) << 4 | bit5_4(w.z) << 8 | bit5_4(w.w) << 12;
+    }
+    uint32_t prev = __shfl_up(bs, 1) >> 15;
+    if (lane == 0) prev = live && off && s[off - 1] == '\\';
+    if (live && (bs | prev)) {
+        bool esc = false;  // the next byte is escaped
+        if (prev) {
+            uint64_t k = off - 1;
+            while (k > 0 && s[k - 1] == '\\') k--;
+            esc = ((off - k) & 1) != 0;
+        }
+        uint32_t e = 0;
+        for (uint32_t k = 0; k < 16; k++) {
+            if (esc) e |= 1u << k, esc = false;
+            else esc = (bs >> k) & 1u;
+        }
+        r.q &= ~e;
+    }
+    return r;
+}
+// bit k: the parity of the set bits 0..k of the 16-bit mask
+__device__ __forceinline__ uint32_t prefix_xor16(uint32_t m) {
+    m ^= m << 1;
+    m ^= m << 2;
+    m ^= m << 4;
+    m ^= m << 8;
+    return m & 0xFFFFu;
+}
+__device__ __forceinline__ uint32_t wave_incl_xor(uint32_t v, uint32_t lane) {
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(v, o);
+        if (lane >= o) v ^= t;
+    }
+    return v;
+}
+constexpr uint32_t FR_WAVES = FR_THREADS / 64;
+// the block's exclusive prefix of v over its 256 lanes and the block's total; wt: one
+// of two sets of wave totals (a step's are read while the next step's are written)
+template <bool XOR>
+__device__ __forceinline__ uint32_t block_excl(uint32_t v, uint32_t lane, uint32_t wave, uint32_t* wt, uint32_t& all) {
+    const uint32_t incl = XOR ? wave_incl_xor(v, lane) : wave_incl(v, lane);
+    if (lane == 63) wt[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0;
+    all = 0;
+    for (uint32_t w = 0; w < FR_WAVES; w++) {
+        const uint32_t t = wt[w];
+        if (XOR) {
+            if (w < wave) before ^= t;
+            all ^= t;
+        } else {
+            if (w < wave) before += t;
+            all += t;
+        }
+    }
+    return XOR ? before ^ incl ^ v : before + incl - v;
+}
+
+// FrameScan's object half for an item of the list: the item is at depth 2
+struct ItemScan {
+    JRd* r;
+    uint8_t next = F_NONE;
+    bool host = false, root_obj = false, in_meta = false;
+    uint32_t seen_obj = 0, seen_meta = 0;
+    uint8_t flags = 0;
+    Span uid{0, 0}, rv{0, 0}, name{0, 0}, ns{0, 0};
+
+    __device__ uint8_t first(uint32_t& seen, int bit, uint8_t c) {
+        if (seen & (1u << bit)) return F_NONE;
+        seen |= 1u << bit;
+        return c;
+    }
+    __device__ void key(int d, const JTok& t) {
+        next = F_NONE;
+        const bool routed = d == 2 || (d == 3 && in_meta);
+        if (!routed) return;
+        if (t.esc) {  // a routed key is compared as decoded text: the host framer decides the item
+            host = true;
+            return;
+        }
+        if (d == 2) {
+            if (lit_eq(*r, t.off, t.len, "metadata")) next = first(seen_obj, 0, F_META);
+        } else {
+            if (lit_eq(*r, t.off, t.len, "uid")) next = first(seen_meta, 0, F_UID);
+            else if (lit_eq(*r, t.off, t.len, "resourceVersion")) next = first(seen_meta, 1, F_RV);
+            else if (lit_eq(*r, t.off, t.len, "name")) next = first(seen_meta, 2, F_NAME);
+            else if (lit_eq(*r, t.off, t.len, "namespace")) next = first(seen_meta, 3, F_NS);
+        }
+    }
+    __device__ void scalar(int d, const JTok& t, bool pa) {
+        if (pa || d != 4 || !in_meta || t.kind != J_STR) return;  // (a non-string value: an empty span)
+        const Span s = t.len ? Span{(uint32_t)t.off, t.len} : Span{0, 0};
+        switch (next) {
+            case F_UID: uid = s; if (t.esc) flags |= KWOK_FRAME_ESC_UID; break;
+            case F_RV: rv = s; if (t.esc) flags |= KWOK_FRAME_ESC_RV; break;
+            case F_NAME: name = s; if (t.esc) flags |= KWOK_FRAME_ESC_NAME; break;
+            case F_NS: ns = s; if (t.esc) flags |= KWOK_FRAME_ESC_NS; break;
+            default: break;
+        }
+    }
+    __device__ void begin(int d, bool a, bool pa) {
+        if (d == 2) {
+            root_obj = !a;
+            return;
+        }
+        if (!pa && d == 3 && next == F_META && !a) in_meta = true;
+    }
+    __device__ void end(int d, bool, bool) {
+        if (d == 3) in_meta = false;
+    }
+};
+}  // namespace
+
+// tile_q[i]: the unescaped quotes of tile i; tile_d0 / tile_d1[i]: its net depth change
+// when it is entered outside / inside a string
+__global__ __launch_bounds__(FR_THREADS) void k_list_quotes(const uint8_t* s, uint64_t len, uint32_t* tile_q,
+                                                           uint32_t* tile_d0, uint32_t* tile_d1) {
+    __shared__ uint32_t wx[2][FR_WAVES];
+    __shared__ uint32_t red[3][FR_WAVES];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t state = 0;  // the in-string parity at the step's start, the tile entered outside a string
+    uint32_t nq = 0, d0 = 0, d1 = 0;
+    for (uint32_t q = 0; q < FR_STEPS; q++) {
+        const uint64_t off = (uint64_t)blockIdx.x * KWOK_WATCH_TILE_BYTES + (uint64_t)q * FR_STEP + tid * 16u;
+        const LWin w = list_window(s, off, len, lane);
+        const uint32_t c = __popc(w.q);
+        uint32_t all;
+        const uint32_t in = state ^ block_excl<true>(c & 1u, lane, wave, wx[q & 1], all);
+        state ^= all;
+        const uint32_t str = prefix_xor16(w.q) ^ (in ? 0xFFFFu : 0u);  // the window's bytes inside a string
+        nq += c;
+        d0 += __popc(w.open & ~str) - __popc(w.close & ~str);
+        d1 += __popc(w.open & str) - __popc(w.close & str);
+    }
+    for (uint32_t o = 32; o; o >>= 1) nq += __shfl_down(nq, o), d0 += __shfl_down(d0, o), d1 += __shfl_down(d1, o);
+    if (lane == 0) red[0][wave] = nq, red[1][wave] = d0, red[2][wave] = d1;
+    __syncthreads();
+    if (tid < 3) {
+        uint32_t t = 0;
+        for (uint32_t w = 0; w < FR_WAVES; w++) t += red[tid][w];
+        (tid == 0 ? tile_q : tid == 1 ? tile_d0 : tile_d1)[blockIdx.x] = t;
+    }
+}
+
+// tile_d0[i] <- the depth change of tile i for the state it is entered in
+__global__ void k_list_pick(const uint32_t* q_base, uint32_t* tile_d0, const uint32_t* tile_d1, uint32_t n_tiles) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_tiles && (q_base[i] & 1u)) tile_d0[i] = tile_d1[i];
+}
+
+// EMIT false: tile_s / tile_e[i] = the candidate starts / ends of tile i (a `{` that
+// raises the depth 2 -> 3, a `}` that lowers it 3 -> 2), and the root arrays' brackets
+// in lc.  EMIT true: tile_s / tile_e are the scanned bases; starts / ends[rank] = offset.
+template <bool EMIT>
+__global__ __launch_bounds__(FR_THREADS) void k_list_split(const uint8_t* s, uint64_t len, const uint32_t* q_base,
+                                                          const uint32_t* d_base, uint32_t* tile_s, uint32_t* tile_e,
+                                                          uint32_t* starts, uint32_t* ends, uint32_t n_cand, uint32_t* lc) {
+    __shared__ uint32_t wx[2][FR_WAVES], wd[2][FR_WAVES], wr[2][FR_WAVES];
+    __shared__ uint32_t red[2][FR_WAVES];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t state = q_base[blockIdx.x] & 1u;
+    uint32_t depth = d_base[blockIdx.x];
+    uint32_t run_s = EMIT ? tile_s[blockIdx.x] : 0u, run_e = EMIT ? tile_e[blockIdx.x] : 0u;
+    uint32_t cnt = 0;  // starts in the low half, ends in the high half (a tile holds at most 16384 of each)
+    for (uint32_t q = 0; q < FR_STEPS; q++) {
+        const uint64_t off = (uint64_t)blockIdx.x * KWOK_WATCH_TILE_BYTES + (uint64_t)q * FR_STEP + tid * 16u;
+        const LWin w = list_window(s, off, len, lane);
+        uint32_t all;
+        const uint32_t in = state ^ block_excl<true>(__popc(w.q) & 1u, lane, wave, wx[q & 1], all);
+        state ^= all;
+        const uint32_t str = prefix_xor16(w.q) ^ (in ? 0xFFFFu : 0u);
+        const uint32_t op = w.open & ~str, cl = w.close & ~str;
+        uint32_t d = depth + block_excl<false>(__popc(op) - __popc(cl), lane, wave, wd[q & 1], all);
+        depth += all;
+        // the window's brackets in order; only depths 1..3 matter
+        uint32_t m = op | cl, c = 0, sm = 0, em = 0;
+        if (m && d <= 19u) {
+            while (m) {
+                const uint32_t b = (uint32_t)__builtin_ctz(m), bit = 1u << b;
+                m &= m - 1;
+                const bool brace = (w.brace & bit) != 0;
+                if (op & bit) {
+                    if (d == 2 && brace) c += 1u, sm |= bit;
+                    if (!EMIT && d == 1 && !brace) atomicAdd(lc + LC_OPEN_N, 1u), atomicMin(lc + LC_OPEN_POS, (uint32_t)(off + b));
+                    d++;
+                } else {
+                    d--;
+                    if (d == 2 && brace) c += 0x10000u, em |= bit;
+                    if (!EMIT && d == 1 && !brace) atomicAdd(lc + LC_CLOSE_N, 1u), atomicMax(lc + LC_CLOSE_POS, (uint32_t)(off + b));
+                }
+            }
+        }
+        if (!EMIT) {
+            cnt += c;
+        } else {
+            const uint32_t ex = block_excl<false>(c, lane, wave, wr[q & 1], all);
+            uint32_t ks = run_s + (ex & 0xFFFFu), ke = run_e + (ex >> 16);
+            while (sm) {
+                const uint32_t b = (uint32_t)__builtin_ctz(sm);
+                sm &= sm - 1;
+                if (ks < n_cand) starts[ks] = (uint32_t)(off + b);
+                ks++;
+            }
+            while (em) {
+                const uint32_t b = (uint32_t)__builtin_ctz(em);
+                em &= em - 1;
+                if (ke < n_cand) ends[ke] = (uint32_t)(off + b);
+                ke++;
+            }
+            run_s += all & 0xFFFFu, run_e += all >> 16;
+        }
+    }
+    if (!EMIT) {
+        uint32_t a = cnt & 0xFFFFu, b = cnt >> 16;  // (a lane's four windows: at most 64 of each)
+        for (uint32_t o = 32; o; o >>= 1) a += __shfl_down(a, o), b += __shfl_down(b, o);
+        if (lane == 0) red[0][wave] = a, red[1][wave] = b;
+        __syncthreads();
+        if (tid < 2) {
+            uint32_t t = 0;
+            for (uint32_t w = 0; w < FR_WAVES; w++) t += red[tid][w];
+            (tid == 0 ? tile_s : tile_e)[blockIdx.x] = t;
+        }
+    }
+}
+
+// lc[LC_R0], lc[LC_R1]: the candidates whose `{` lies inside the root array (open, close)
+__global__ void k_list_range(const uint32_t* starts, uint32_t n_cand, uint32_t open, uint32_t close, uint32_t* lc) {
+    if (threadIdx.x > 1 || blockIdx.x) return;
+    const uint32_t key = threadIdx.x ? close : open;
+    uint32_t lo = 0, hi = n_cand;
+    while (lo < hi) {  // the first candidate past key
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (starts[mid] > key) hi = mid;
+        else lo = mid + 1;
+    }
+    lc[threadIdx.x ? LC_R1 : LC_R0] = lo;
+}
+
+// one thread per item r0 + i: the gap before it, its parse over exactly its span, its frame
+__global__ __launch_bounds__(256) void k_list_parse(const uint8_t* s, const uint32_t* starts, const uint32_t* ends, uint32_t r0,
+                                                    uint32_t n, uint32_t open, uint32_t close, kwok_watch_frame* frames,
+                                                    uint32_t* host_list, uint32_t* lc) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const jpos lo = starts[r0 + i], last = ends[r0 + i], hi = last + 1u;
+    const jpos gap = i ? ends[r0 + i - 1] + 1u : open + 1u;
+    kwok_watch_frame f;
+    f.line_off = f.doc_off = lo;
+    f.doc_len = hi - lo;
+    f.type = KWOK_WATCH_ADDED, f.flags = 0, f.status = KWOK_OK, f.reserved0 = 0;
+    f.uid = f.resource_version = f.name = f.namespace_ = kwok_str{0, 0};
+    // (spans the depth count paired wrongly - an invalid body - are not read at all)
+    bool ok = gap <= lo && lo < last && last < close;
+    if (ok) {
+        JRd rd{s, gap, close, ~0u, make_uint4(0, 0, 0, 0)};
+        uint32_t commas = 0;
+        for (jpos p = gap; p < lo && ok; p++) {
+            const uint32_t c = rd.at(p);
+            if (c == ',') ok = ++commas <= (i ? 1u : 0u);
+            else ok = c == ' ' || c == '\t' || c == '\n' || c == '\r';
+        }
+        ok = ok && commas == (i ? 1u : 0u);
+        if (ok && i == n - 1)
+            for (jpos p = hi; p < close && ok; p++) {
+                const uint32_t c = rd.at(p);
+                ok = c == ' ' || c == '\t' || c == '\n' || c == '\r';
+            }
+    }
+    if (ok) {
+        JRd rd{s, lo, hi, ~0u, make_uint4(0, 0, 0, 0)};
+        ItemScan p;
+        p.r = &rd;
+        ok = jparse(rd, p, 2) && p.root_obj && rd.pos == hi;
+        if (ok && p.host) {
+            host_list[atomicAdd(lc + LC_HOST, 1u)] = i;  // (its frame is the host framer's)
+        } else if (ok) {
+            f.flags = p.flags;
+            f.uid = kwok_str{p.uid.off, p.uid.len};
+            f.resource_version = kwok_str{p.rv.off, p.rv.len};
+            f.name = kwok_str{p.name.off, p.name.len};
+            f.namespace_ = kwok_str{p.ns.off, p.ns.len};
+        }
+    }
+    if (!ok) atomicOr(lc + LC_BAD, 1u);
+    frames[i] = f;
+}
+
+void launch_list_quotes(const uint8_t* s, uint64_t len, uint32_t n_tiles, uint32_t* tile_q, uint32_t* tile_d0,
+                        uint32_t* tile_d1, hipStream_t st) {
+    if (n_tiles) hipLaunchKernelGGL(k_list_quotes, dim3(n_tiles), dim3(FR_THREADS), 0, st, s, len, tile_q, tile_d0, tile_d1);
+}
+void launch_list_pick(const uint32_t* q_base, uint32_t* tile_d0, const uint32_t* tile_d1, uint32_t n_tiles, hipStream_t st) {
+    if (n_tiles) hipLaunchKernelGGL(k_list_pick, dim3((n_tiles + 255) / 256), dim3(256), 0, st, q_base, tile_d0, tile_d1, n_tiles);
+}
+void launch_list_count(const uint8_t* s, uint64_t len, uint32_t n_tiles, const uint32_t* q_base, const uint32_t* d_base,
+                       uint32_t* tile_s, uint32_t* tile_e, uint32_t* lc, hipStream_t st) {
+    if (n_tiles)
+        hipLaunchKernelGGL(k_list_split<false>, dim3(n_tiles), dim3(FR_THREADS), 0, st, s, len, q_base, d_base, tile_s, tile_e,
+                           (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, lc);
+}
+void launch_list_emit(const uint8_t* s, uint64_t len, uint32_t n_tiles, const uint32_t* q_base, const uint32_t* d_base,
+                      uint32_t* s_base, uint32_t* e_base, uint32_t* starts, uint32_t* ends, uint32_t n_cand, hipStream_t st) {
+    if (n_tiles && n_cand)
+        hipLaunchKernelGGL(k_list_split<true>, dim3(n_tiles), dim3(FR_THREADS), 0, st, s, len, q_base, d_base, s_base, e_base,
+                           starts, ends, n_cand, (uint32_t*)nullptr);
+}
+void launch_list_range(const uint32_t* starts, uint32_t n_cand, uint32_t open, uint32_t close, uint32_t* lc, hipStream_t st) {
+    hipLaunchKernelGGL(k_list_range, dim3(1), dim3(64), 0, st, starts, n_cand, open, close, lc);
+}
+void launch_list_parse(const uint8_t* s, const uint32_t* starts, const uint32_t* ends, uint32_t r0, uint32_t n, uint32_t open,
+                       uint32_t close, kwok_watch_frame* frames, uint32_t* host_list, uint32_t* lc, hipStream_t st) {
+    if (!n) return;
+    const uint32_t bs = json_block(n);
+    hipLaunchKernelGGL(k_list_parse, dim3((n + bs - 1) / bs), dim3(bs), 0, st, s, starts, ends, r0, n, open, close, frames,
+                       host_list, lc);
+}
 }  // namespace kwok

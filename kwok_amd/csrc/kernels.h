@@ -302,6 +302,36 @@ void launch_frame_emit(const uint8_t* s, uint64_t len, uint32_t n_tiles, const u
 void launch_frame_parse(const uint8_t* s, const uint32_t* ends, uint32_t n, kwok_watch_frame* frames, uint32_t* host_list,
                         uint32_t* n_host, hipStream_t st);
 
+// ---- the List body framer (json.hip, kwok_watch.h): the same buffer and tiles ----
+enum : uint32_t {  // the framer's device counters lc[KWOK_LIST_COUNTERS], read back by engine.cpp
+    LC_QUOTES = 0,  // unescaped quotes of the body (odd: it ends inside a string)
+    LC_DEPTH,       // the depth at the body's end (not 0: unbalanced)
+    LC_STARTS,      // `{` that raise the depth 2 -> 3
+    LC_ENDS,        // `}` that lower it 3 -> 2
+    LC_OPEN_N, LC_OPEN_POS,    // `[` directly under the root: how many, the first one's offset (zeroed to ~0)
+    LC_CLOSE_N, LC_CLOSE_POS,  // `]` that close them: how many, the last one's offset
+    LC_R0, LC_R1,   // the candidates inside the root array: ranks [R0, R1)
+    LC_BAD,         // an item or a gap failed
+    LC_HOST,        // items listed for the host framer
+    KWOK_LIST_COUNTERS = 16
+};
+// per tile: unescaped quotes, and the net depth change entered outside / inside a string
+void launch_list_quotes(const uint8_t* s, uint64_t len, uint32_t n_tiles, uint32_t* tile_q, uint32_t* tile_d0,
+                        uint32_t* tile_d1, hipStream_t st);
+// tile_d0[i] <- tile_d1[i] where q_base[i] (the quotes before tile i) is odd
+void launch_list_pick(const uint32_t* q_base, uint32_t* tile_d0, const uint32_t* tile_d1, uint32_t n_tiles, hipStream_t st);
+// per tile: the `{` 2 -> 3 and `}` 3 -> 2; lc[LC_OPEN_*], lc[LC_CLOSE_*]
+void launch_list_count(const uint8_t* s, uint64_t len, uint32_t n_tiles, const uint32_t* q_base, const uint32_t* d_base,
+                       uint32_t* tile_s, uint32_t* tile_e, uint32_t* lc, hipStream_t st);
+// starts / ends[k] = the offset of the k-th such `{` / `}` (k < n_cand); s_base / e_base: the scanned counts
+void launch_list_emit(const uint8_t* s, uint64_t len, uint32_t n_tiles, const uint32_t* q_base, const uint32_t* d_base,
+                      uint32_t* s_base, uint32_t* e_base, uint32_t* starts, uint32_t* ends, uint32_t n_cand, hipStream_t st);
+// lc[LC_R0], lc[LC_R1]: the candidates that start inside (open, close)
+void launch_list_range(const uint32_t* starts, uint32_t n_cand, uint32_t open, uint32_t close, uint32_t* lc, hipStream_t st);
+// one thread per item r0 + i (i < n): frames[i], or i listed for the host (lc[LC_HOST]); lc[LC_BAD] on any failure
+void launch_list_parse(const uint8_t* s, const uint32_t* starts, const uint32_t* ends, uint32_t r0, uint32_t n, uint32_t open,
+                       uint32_t close, kwok_watch_frame* frames, uint32_t* host_list, uint32_t* lc, hipStream_t st);
+
 // ---- node batches on the GPU (kwok_ingest_nodes, node_controller.go:256-270) ----
 struct NodeBatch {
     const kwok_node_event* ev;  // [n] on the device or read in place

@@ -117,6 +117,9 @@ def declare(lib, pre):
             "ingest_pods_framed": (C.c_int, [VP, VP, U64, VP, VP, SZ, VP, VP, VP, P(SZ)]),
             "ingest_nodes_framed": (C.c_int, [VP, VP, U64, VP, SZ, VP, VP, P(SZ)]),
             "watch_stats": (C.c_int, [VP, VP]),
+            "frame_list": (C.c_int, [VP, SZ, VP, SZ, P(SZ), VP]),
+            "frame_list_gpu": (C.c_int, [VP, VP, SZ, VP, SZ, P(SZ), VP, P(SZ), P(U64)]),
+            "list_stats": (C.c_int, [VP, VP]),
         })
     for name, (res, args) in sig.items():
         f = getattr(lib, pre + name, None)
@@ -617,6 +620,39 @@ class Engine(EngineBase):
         out = (C.c_uint64 * len(abi.WATCH_STATS))()
         self._check(self._lib.kwok_watch_stats(self._h, out), "watch_stats")
         return dict(zip(abi.WATCH_STATS, list(out)))
+
+    # ---- List bodies (include/kwok_watch.h): one frame per item, the body resident ----
+    def frame_list(self, body, cap=None):
+        """kwok_frame_list_gpu over one complete List response body: (frames
+        (WATCH_FRAME_DTYPE, every type ADDED), info (abi.ListInfo), items the host
+        framed, stream_id).  The body stays resident as the stream for
+        ingest_pods_framed / ingest_nodes_framed until the next framing call; the
+        engine keeps a reference to the bytes.  KwokError(EINVAL) for a body that is
+        no valid list (nothing stays resident), with .n_frames set when cap (default:
+        a bound on the item count) is smaller than the item count."""
+        buf = np.frombuffer(body, np.uint8) if len(body) else np.zeros(1, np.uint8)
+        n = len(body)
+        nf, nh, sid, info = C.c_size_t(), C.c_size_t(), C.c_uint64(), abi.ListInfo()
+        if cap is None:
+            cap = bytes(body).count(b"{") if not isinstance(body, np.ndarray) else int((body == 123).sum())
+        frames = np.zeros(max(cap, 1), abi.WATCH_FRAME_DTYPE)
+        self._watch_buf = None
+        rc = self._lib.kwok_frame_list_gpu(self._h, buf.ctypes.data, n, frames.ctypes.data, cap, C.byref(nf),
+                                           C.byref(info), C.byref(nh), C.byref(sid))
+        try:
+            self._check(rc, "frame_list_gpu")
+        except KwokError as err:
+            err.n_frames = nf.value
+            raise
+        self._watch_buf = buf
+        return frames[:nf.value], info, nh.value, sid.value
+
+    def list_stats(self):
+        """kwok_list_stats: bodies / items / items framed by the host / bodies handed whole
+        to the host framer / body bytes uploaded"""
+        out = (C.c_uint64 * len(abi.LIST_STATS))()
+        self._check(self._lib.kwok_list_stats(self._h, out), "list_stats")
+        return dict(zip(abi.LIST_STATS, list(out)))
 
     @staticmethod
     def _arena_arg(arena):
