@@ -170,6 +170,66 @@ enum {
 };
 int kwok_list_stats(kwok_engine* e, uint64_t out[KWOK_LIST_STAT_COUNT]);
 
+/* ---- Relist with Replace ---------------------------------------
+ *
+ * A watch that fell behind is closed with 410 Gone; the reference opens a fresh one
+ * (pod_controller.go:280-290, node_controller.go:235-245) and never sees the Deleted
+ * events of the gap.  A resync session closes that gap the way client-go's reflector
+ * does: list again, then remove what the list did not hold.  A session is per kind
+ * (nodes, pods); it collects one `seen` mark per slot and is closed by a sweep.
+ *
+ * Rules:
+ *   - begin: opens the kind's session with every mark cleared; a second begin
+ *     restarts it, marks cleared again.  Marks exist only inside a session;
+ *   - marks: while the kind's session is open, every KWOK_OP_UPSERT record of that
+ *     kind whose final per-record status is KWOK_OK marks the slot of the handle it
+ *     returned - through every ingest entry (kwok_ingest_nodes, kwok_ingest_pods,
+ *     _packed, _packed12, _packed12_tick, kwok_ingest_pods_json,
+ *     kwok_ingest_nodes_json, kwok_ingest_pods_framed, kwok_ingest_nodes_framed),
+ *     records the host completed included (a kwok_pod_rec12 update: its target).
+ *     A DELETE marks nothing, a rejected record marks nothing;
+ *   - kwok_resync_mark: marks objects the caller saw in the list and did not ingest
+ *     (an item it dropped as the echo of the engine's own patch).  A handle out of
+ *     range, in a bucket this rank does not own, or whose slot is not in use is
+ *     counted in *n_bad and marks nothing;
+ *   - sweep: closes the session.  Every live object of the kind without a mark is
+ *     removed in canonical order (ascending handle) with the effect of a Deleted
+ *     watch event for it.  Pods (pod_controller.go:320-343): live is a used slot, a
+ *     delete-pending pod included; the event's status.podIP is the address the slot
+ *     holds, so Put(ip) runs if the node is managed and the address is in the CIDR
+ *     (:329-336; nothing with EnableCNI, :337-342: the caller runs cni.Remove for
+ *     out_node's managed nodes), the slot is freed, a zombie node entry nothing
+ *     references any more goes, and the foreign-IP flag is not raised.  Nodes
+ *     (node_controller.go:265-269): nodesSets.Delete; the entry lives on as a zombie
+ *     while pods reference it.  The removals are DELETE records built on the device
+ *     and run through the ingest's own event switch, so every side effect (heartbeat
+ *     handle bases, the handle-list epoch, quiet-tick state) is a Deleted event's;
+ *   - the sweep drains submitted ticks first, as every ingest does; it is refused
+ *     with KWOK_EINVAL on a multi-rank engine and with the poisoned code on a
+ *     poisoned one.  cap below the number of unmarked objects: KWOK_EINVAL with
+ *     *n_swept set, nothing removed, the session stays open (retry with larger
+ *     arrays);
+ *   - end: closes the session without sweeping.  A sweep or a mark without an open
+ *     session: KWOK_EINVAL, nothing changes. */
+enum { KWOK_KIND_NODES = 0, KWOK_KIND_PODS = 1 };
+int kwok_resync_begin(kwok_engine* e, int kind);
+int kwok_resync_mark(kwok_engine* e, int kind, const int32_t* handles, size_t n, size_t* n_bad);
+/* out_handles[cap]: the swept handles, ascending; *n_swept their number.  Pods,
+ * optional: out_released[i] the address put back for swept pod i (0: none),
+ * out_node[i] its node's handle.  Returns KWOK_OK or an error. */
+int kwok_resync_sweep(kwok_engine* e, int kind, int32_t* out_handles, size_t cap, size_t* n_swept,
+                      uint32_t* out_released, int32_t* out_node);
+int kwok_resync_end(kwok_engine* e, int kind);
+enum {
+    KWOK_RESYNC_STAT_SESSIONS = 0, /* begins */
+    KWOK_RESYNC_STAT_MARKED,       /* marks stored: ingested records + explicit marks */
+    KWOK_RESYNC_STAT_SWEPT_NODES,
+    KWOK_RESYNC_STAT_SWEPT_PODS,
+    KWOK_RESYNC_STAT_RELEASED,     /* addresses the swept pods put back */
+    KWOK_RESYNC_STAT_COUNT
+};
+int kwok_resync_stats(kwok_engine* e, uint64_t out[KWOK_RESYNC_STAT_COUNT]);
+
 #ifdef __cplusplus
 }
 #endif

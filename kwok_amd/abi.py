@@ -116,6 +116,10 @@ LIST_ESC_KIND, LIST_ESC_RV, LIST_ESC_CONTINUE = 1, 2, 4
 LIST_STATS = ("bodies", "items", "host_items", "host_bodies", "body_bytes")  # KWOK_LIST_STAT_* order
 
 
+KIND_NODES, KIND_PODS = 0, 1  # KWOK_KIND_*: the kind of a resync session (relist with Replace)
+RESYNC_STATS = ("sessions", "marked", "swept_nodes", "swept_pods", "released")  # KWOK_RESYNC_STAT_* order
+
+
 class ListInfo(C.Structure):
     """kwok_list_info: the envelope of a List body (offsets into the body)"""
     _fields_ = [("kind", KwokStr), ("resource_version", KwokStr), ("continue_", KwokStr), ("items", KwokStr),

@@ -289,6 +289,9 @@ class Stats:
     list_items: int = 0         # feed_list: items framed
     list_host_items: int = 0    # ... of them by the host framer (an escaped routed key)
     list_bad_bodies: int = 0    # pages that are no valid list: dropped whole
+    resync_swept_nodes: int = 0  # feed_list(replace=True): objects the complete list no longer held, removed
+    resync_swept_pods: int = 0
+    resync_skipped: int = 0     # ... sessions closed without a sweep (a bad page, frame or record: a partial picture)
     bodies: int = 0
     rejected: list = field(default_factory=list)
 
@@ -337,6 +340,7 @@ class Controller:
         self.stats = Stats()
         self.node_name = {}   # node handle -> name
         self.node_handle = {}  # name -> node handle
+        self.node_uid = {}    # node handle -> uid (a swept node's echoes are forgotten)
         self.pod_by_uid = {}
         self.pod_uid = {}     # pod handle -> uid
         self.pod_ref = {}     # pod handle -> (namespace, name)
@@ -349,6 +353,9 @@ class Controller:
         self.fed = set()      # the kinds fed raw bytes since the last step
         self.pages = {True: [], False: []}  # feed_list: complete List bodies per kind, in feed order
         self.list_cursor = {}  # "nodes" / "pods" -> kind, resource_version, continue_ of the kind's last page (decoded text)
+        # feed_list(replace=True): the kind's open resync session (kwok_watch.h), None: none;
+        # dirty: a page, frame or record of it failed - the picture is partial, no sweep
+        self.resync = {True: None, False: None}
 
     def close(self):
         self.eng.close()
@@ -372,17 +379,25 @@ class Controller:
         self.fed.add(bool(nodes))
         self.raw[bool(nodes)] += data
 
-    def feed_list(self, nodes: bool, body: bytes):
+    def feed_list(self, nodes: bool, body: bytes, replace: bool = False):
         """one complete page of the node (nodes=True) or pod List response
         (pod_controller.go:357-368, node_controller.go:282-296): framed and ingested
         at the next step, before the kind's watch bytes and typed events; its items
-        are upserts (objects absent from a list are not deleted).  After the step
-        list_cursor[kind] holds the page's resourceVersion and continue token: the
-        caller requests the next page with the token, or opens its watch from the
-        version."""
+        are upserts.  After the step list_cursor[kind] holds the page's
+        resourceVersion and continue token: the caller requests the next page with
+        the token, or opens its watch from the version.
+
+        replace=True (a relist after 410 Gone, client-go's Replace): the page opens
+        the kind's resync session when it is flushed, if none is open; the session
+        ends with the flushed page whose continue token is empty, and every node or
+        pod the engine holds that no page, watch event or typed event of the session
+        touched is then removed as a Deleted event would remove it (kwok_resync_sweep),
+        before the same step's typed events and watch bytes of the kind.  A session
+        with a bad page, a bad frame or a rejected record is closed without a sweep
+        (Stats.resync_skipped): the caller lists again."""
         if not hasattr(self.eng, "frame_list"):
             raise ValueError("feed_list needs the engine backend (kwok_frame_list_gpu)")
-        self.pages[bool(nodes)].append(bytes(body))
+        self.pages[bool(nodes)].append((bytes(body), bool(replace)))
 
     def on_event(self, nodes: bool, typ: str, obj: dict):
         if bool(nodes) in self.fed:
@@ -415,12 +430,14 @@ class Controller:
         nb = self._encode(nw)
         pb = self._encode(pw)
         pages, self.pages = self.pages, {True: [], False: []}
-        for body in pages[True]:  # a kind's list pages go first, in feed order: the watch starts at their version
+        for body, replace in pages[True]:  # a kind's list pages go first, in feed order: the watch starts at their version
+            self._open_resync(True, replace)
             self._flush_list(True, body)
         self._flush_nodes(nb)
         if True in fed:
             self._flush_watch(True)
-        for body in pages[False]:
+        for body, replace in pages[False]:
+            self._open_resync(False, replace)
             self._flush_list(False, body)
         self._flush_pods(pb)
         if False in fed:
@@ -483,6 +500,7 @@ class Controller:
             if recs[k]["op"] == abi.OP_DELETE:
                 self.node_name.pop(int(hs[k]), None)
                 self.node_handle.pop(names[k], None)
+                self.node_uid.pop(int(hs[k]), None)
             else:
                 self.node_name[int(hs[k])] = names[k]
                 self.node_handle[names[k]] = int(hs[k])
@@ -505,9 +523,11 @@ class Controller:
             if w.deleted:
                 self.node_name.pop(int(hs[k]), None)
                 self.node_handle.pop(name, None)
+                self.node_uid.pop(int(hs[k]), None)
             else:
                 self.node_name[int(hs[k])] = name
                 self.node_handle[name] = int(hs[k])
+                self.node_uid[int(hs[k])] = w.uid
 
     def _spec_id(self, b, d):
         spec = (tuple((b.text(c.name), b.text(c.image)) for c in d.containers[:d.n_containers]),
@@ -609,18 +629,29 @@ class Controller:
         self.stats.watch_host_frames += n_host
         self._ingest_frames(nodes, stream, frames, sid)
 
+    def _open_resync(self, nodes, replace):
+        """a page fed with replace=True opens the kind's resync session, if none is open"""
+        if replace and self.resync[nodes] is None:
+            self.eng.resync_begin(abi.KIND_NODES if nodes else abi.KIND_PODS)
+            self.resync[nodes] = {"dirty": False}
+
     def _flush_list(self, nodes, body):
         """one List page: framed on the GPU, its items taken as upserts by the path
         of the watch frames (an item whose (uid, resourceVersion) is an echo of the
-        engine's own patch is dropped); the page's resourceVersion and continue
-        token go to list_cursor.  A body that is no valid list is counted and
-        dropped (client-go: the List call fails, the caller lists again)."""
+        engine's own patch is dropped; inside a resync session its known handle is
+        marked instead); the page's resourceVersion and continue token go to
+        list_cursor.  A body that is no valid list is counted and dropped (client-go:
+        the List call fails, the caller lists again).  The page that completes a
+        list (an empty continue token) ends the kind's open resync session."""
+        sess = self.resync[nodes]
         try:
             frames, info, n_host, sid = self.eng.frame_list(body)
         except KwokError as err:
             if err.code != abi.EINVAL:
                 raise
             self.stats.list_bad_bodies += 1
+            if sess is not None:
+                sess["dirty"] = True
             return
         self.stats.list_items += len(frames)
         self.stats.list_host_items += n_host
@@ -628,19 +659,55 @@ class Controller:
             kind=list_text(body, info.kind, info.flags & abi.LIST_ESC_KIND),
             resource_version=list_text(body, info.resource_version, info.flags & abi.LIST_ESC_RV),
             continue_=list_text(body, info.continue_, info.flags & abi.LIST_ESC_CONTINUE))
-        self._ingest_frames(nodes, body, frames, sid)
+        self._ingest_frames(nodes, body, frames, sid, sess)
+        if sess is not None and not self.list_cursor["nodes" if nodes else "pods"]["continue_"]:
+            self._end_resync(nodes)  # the list is complete
 
-    def _ingest_frames(self, nodes, stream, frames, sid):
+    def _end_resync(self, nodes):
+        """the kind's resync session ends: the sweep (kwok_resync_sweep) of what the complete
+        list did not hold, and the bookkeeping of the swept objects - or, after a bad page,
+        frame or rejected record, no sweep at all (a sweep deletes: never on a partial picture)"""
+        kind = abi.KIND_NODES if nodes else abi.KIND_PODS
+        sess, self.resync[nodes] = self.resync[nodes], None
+        if sess["dirty"]:
+            self.eng.resync_end(kind)
+            self.stats.resync_skipped += 1
+            return
+        hs, _rel, nd = self.eng.resync_sweep(kind)
+        if nodes:
+            for h in hs.tolist():
+                self.node_handle.pop(self.node_name.pop(h, None), None)
+                self.echo.forget(self.node_uid.pop(h, None))
+            self.stats.resync_swept_nodes += len(hs)
+            return
+        for h, n in zip(hs.tolist(), nd.tolist()):
+            uid = self.pod_uid.get(h)
+            # EnableCNI: cni.Remove for a swept pod on a managed node (pod_controller.go:337-342), before its
+            # handle's bookkeeping goes (_flush_pods_gpu's order); its node from the sweep: there is no document
+            if self.conf.enable_cni and self.conf.cni and h in self.pod_ref and self.has(self.node_name.get(n, "")):
+                ns, name = self.pod_ref[h]
+                self.conf.cni.remove(uid, name, ns)
+            self.pod_uid.pop(h, None)
+            self.pod_ref.pop(h, None)
+            self.pod_by_uid.pop(uid, None)
+            self.echo.forget(uid)
+        self.stats.resync_swept_pods += len(hs)
+
+    def _ingest_frames(self, nodes, stream, frames, sid, sess=None):
         """step 1-3 over the frames of the resident stream (a watch stream's lines or
-        a List body's items)"""
+        a List body's items).  sess: the page's open resync session (_flush_list)"""
         def text(f, key, bit):
             raw = stream[int(f[key]["off"]):int(f[key]["off"]) + int(f[key]["len"])]
             return json.loads(b'"' + raw + b'"') if f["flags"] & bit else raw.decode()
 
-        keep, uids, deleted, seen = [], [], [], set()
+        name = lambda i: text(frames[i], "name", abi.FRAME_ESC_NAME)  # noqa: E731
+        ns = lambda i: text(frames[i], "namespace_", abi.FRAME_ESC_NS)  # noqa: E731
+        keep, uids, deleted, seen, echoed = [], [], [], set(), []
         for i, f in enumerate(frames):
             if f["status"] != abi.OK:
                 self.stats.watch_bad_frames += 1
+                if sess is not None:
+                    sess["dirty"] = True
                 continue
             if f["type"] in (abi.WATCH_BOOKMARK, abi.WATCH_ERROR):
                 self.stats.watch_skipped += 1
@@ -651,6 +718,8 @@ class Controller:
             dl = f["type"] == abi.WATCH_DELETED
             if self.suppress and not dl and self.echo.is_echo(uid, rv) and uid not in seen:
                 self.stats.echoes_at_flush += 1
+                if sess is not None:  # seen in the list, not ingested: marked by its known handle
+                    echoed.append(self.node_handle.get(name(i), -1) if nodes else self.pod_by_uid.get(uid, -1))
                 continue
             seen.add(uid)
             if dl:
@@ -658,11 +727,13 @@ class Controller:
             keep.append(i)
             uids.append(uid)
             deleted.append(dl)
+        echoed = [h for h in echoed if h >= 0]
+        if echoed:
+            self.eng.resync_mark(abi.KIND_NODES if nodes else abi.KIND_PODS, echoed)
         if not keep:
             return
         keep = np.array(keep, np.uint32)
-        name = lambda i: text(frames[i], "name", abi.FRAME_ESC_NAME)  # noqa: E731
-        ns = lambda i: text(frames[i], "namespace_", abi.FRAME_ESC_NS)  # noqa: E731
+        partial = (abi.EDOMAIN, abi.EINVAL, abi.EFULL)  # a rejected record: the session's picture is partial
         if nodes:
             hs, st, nh = self.eng.ingest_nodes_framed(self.codec, sid, keep)
             self.stats.node_docs_host += nh
@@ -671,13 +742,17 @@ class Controller:
                 if st[k] != abi.OK:
                     if st[k] in (abi.EDOMAIN, abi.EINVAL):
                         self.stats.rejected.append(("node", name(i), int(st[k])))
+                    if sess is not None and st[k] in partial:
+                        sess["dirty"] = True
                     continue
                 if deleted[k]:
                     self.node_name.pop(int(hs[k]), None)
                     self.node_handle.pop(name(i), None)
+                    self.node_uid.pop(int(hs[k]), None)
                 else:
                     self.node_name[int(hs[k])] = name(i)
                     self.node_handle[name(i)] = int(hs[k])
+                    self.node_uid[int(hs[k])] = uids[k]
             return
         n_host = [0]
 
@@ -693,6 +768,8 @@ class Controller:
         for k, i in enumerate(keep):
             if st[k] not in (abi.OK, NOT_SENT):
                 self.stats.rejected.append(("pod", name(i), int(st[k])))
+                if sess is not None and st[k] in partial:
+                    sess["dirty"] = True
                 continue
             if deleted[k]:
                 # EnableCNI: cni.Remove for a pod on a managed node, before its handle's bookkeeping

@@ -277,6 +277,25 @@ struct kwok_engine {
         uint64_t lstats[KWOK_LIST_STAT_COUNT] = {};
     } watch;
 
+    // ---- relist with Replace (resync.hip, kwok_watch.h): a `seen` byte per slot of each
+    // kind (allocated at the kind's first begin), the sweep's tile counts and outputs ----
+    struct Resync {
+        uint8_t* pod_seen = nullptr;   // [PLa] re-laid out with the pod arrays (grow_pods)
+        uint8_t* node_seen = nullptr;  // [NLa]
+        bool open[2] = {false, false}; // KWOK_KIND_*: a session is open (the ingests mark)
+        ResyncCounters* ctr = nullptr;    // device
+        ResyncCounters* ctr_h = nullptr;  // pinned
+        uint32_t *tile_cnt = nullptr, *tile_base = nullptr;
+        size_t tile_cap = 0;
+        uint32_t* total = nullptr;     // device [1]
+        uint32_t* total_h = nullptr;   // pinned [1]
+        int32_t *d_handles = nullptr, *d_nodes = nullptr;  // [out_cap] the swept handles / their nodes, emit order
+        size_t out_cap = 0;
+        int32_t* d_mark = nullptr;     // [mark_cap] kwok_resync_mark's handles
+        size_t mark_cap = 0;
+        uint64_t stats[KWOK_RESYNC_STAT_COUNT] = {};
+    } resync;
+
     // ---- the pod codec on the GPU (json.hip): per-document buffers, the codec's
     // selectors, the spec table (kwok_spec_key -> spec id) ----
     struct Json {
@@ -879,6 +898,7 @@ int grow_pods(kwok_engine* e, uint32_t new_cp) {
         (rc = relayout(S.pod_ctime)) || (rc = relayout(S.pod_ip)) || (rc = relayout(S.host_ip)) ||
         (rc = resize(S.alloc_addr, false)) || (rc = resize(S.use_list, false)) || (rc = resize(S.rel_list, false)))
         return rc;
+    if (e->resync.pod_seen && (rc = relayout(e->resync.pod_seen))) return rc;  // (a growth inside a session keeps the marks)
     for (auto& T : e->slots) {
         if (!T.alloc) continue;
         if ((rc = resize(T.pp_pods, true)) || (rc = resize(T.pp_off, true)) || (rc = resize(T.pp_len, true)) ||
@@ -1205,6 +1225,14 @@ void kwok_engine_destroy(kwok_engine* e) {
             if (p) (void)hipFree(p);
         if (Wt.counts_h) (void)hipHostFree(Wt.counts_h);
         if (Wt.lc_h) (void)hipHostFree(Wt.lc_h);
+    }
+    {
+        auto& R = e->resync;
+        void* rp[] = {R.pod_seen, R.node_seen, R.ctr, R.tile_cnt, R.tile_base, R.total, R.d_handles, R.d_nodes, R.d_mark};
+        for (void* p : rp)
+            if (p) (void)hipFree(p);
+        if (R.ctr_h) (void)hipHostFree(R.ctr_h);
+        if (R.total_h) (void)hipHostFree(R.total_h);
     }
     if (e->h_xall) (void)hipHostFree(e->h_xall);
     if (e->pinned) (void)hipHostFree(e->pinned);
@@ -1864,6 +1892,10 @@ int ingest_nodes_impl(kwok_engine* e, const kwok_node_event* ev, size_t n, const
         N.force = 1;
         if ((rc = sort_apply_results())) return failed(rc);
     }
+    if (e->resync.open[KWOK_KIND_NODES]) {  // the batch's final results mark their nodes (before the buffers' next use)
+        launch_seen_mark_nodes(e->S, N, e->resync.node_seen, e->resync.ctr, st);
+        HIPCHK(e, hipGetLastError());
+    }
     const auto t2 = clk::now();
     if (out_handles) memcpy(out_handles, G.res_h, n * 4);
     if (out_status) memcpy(out_status, G.res_h + n, n * 4);
@@ -2097,6 +2129,16 @@ int ingest_pods_impl(kwok_engine* e, const void* recs, int packed, size_t n, con
     // has (or an earlier chunk did).  One read-back of the chunks' summaries at the
     // end: the rare chunk that needs growth and the chunks after it are then applied
     // again with the host in the loop (ingest_chunk), in order.
+    // an open pod session (kwok_watch.h): the chunk's final results mark their pods, behind its apply
+    // pass on the engine stream and before its buffers' next use (spec: as the pass, nothing when the
+    // chunk returned for growth; the redo marks then)
+    auto mark_seen = [&](IngestBatch I, bool spec) -> int {
+        if (!e->resync.open[KWOK_KIND_PODS]) return KWOK_OK;
+        I.spec = spec ? 1u : 0u;
+        launch_seen_mark_pods(e->S, I, e->resync.pod_seen, e->resync.ctr, st);
+        HIPCHK(e, hipGetLastError());
+        return KWOK_OK;
+    };
     int tick_k = -1;  // tick mode: the slot of the tick queued behind the batch
     auto run = [&]() -> int {
         HIPCHK(e, hipEventRecord(G.go, st));
@@ -2115,6 +2157,7 @@ int ingest_pods_impl(kwok_engine* e, const void* recs, int packed, size_t n, con
             if (e->debug_fail_chunk == k + 1) return e->fail(KWOK_EDEVICE, "injected failure of ingest chunk %u", k);
             if (int r = enqueue_sort_need(e, I)) return r;
             if (int r = enqueue_apply(e, I, true)) return r;
+            if (int r = mark_seen(I, true)) return r;
             if (tstamp) HIPCHK(e, hipEventRecord(G.tev[4 + k], st));  // 4 / 5: chunk k applied
             // chunk k's results on the results stream; its accumulator set free for chunk k + 2
             HIPCHK(e, hipEventRecord(G.used[k & 1], st));
@@ -2185,6 +2228,7 @@ int ingest_pods_impl(kwok_engine* e, const void* recs, int packed, size_t n, con
             e->ing_chunk = k;
             const int r = ingest_chunk(e, chunk_batch(k));
             if (r < 0) return r;
+            if (int r2 = mark_seen(chunk_batch(k), false)) return r2;
             if (e->debug_fail_apply == k + 1)
                 return e->fail(KWOK_EDEVICE, "injected failure after the apply pass of ingest chunk %u", k);
             rejected += r;
@@ -3235,6 +3279,200 @@ int kwok_frame_list_gpu(kwok_engine* e, const char* body, size_t len, kwok_watch
 int kwok_list_stats(kwok_engine* e, uint64_t out[KWOK_LIST_STAT_COUNT]) {
     if (!e || !out) return KWOK_EINVAL;
     for (int k = 0; k < KWOK_LIST_STAT_COUNT; k++) out[k] = e->watch.lstats[k];
+    return KWOK_OK;
+}
+
+// ---- relist with Replace (kwok_watch.h) ---------------------------
+namespace {
+bool resync_kind_ok(int kind) { return kind == KWOK_KIND_NODES || kind == KWOK_KIND_PODS; }
+int resync_read_counters(kwok_engine* e) {
+    auto& R = e->resync;
+    HIPCHK(e, hipMemcpyAsync(R.ctr_h, R.ctr, sizeof(ResyncCounters), hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    return KWOK_OK;
+}
+}  // namespace
+
+int kwok_resync_begin(kwok_engine* e, int kind) {
+    if (!e || !resync_kind_ok(kind)) return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    auto& R = e->resync;
+    if (!R.ctr) {
+        if (int rc = dalloc(e, &R.ctr, 1)) return rc;
+        if (int rc = dalloc(e, &R.total, 1)) return rc;
+        if (hipHostMalloc((void**)&R.ctr_h, sizeof(ResyncCounters), hipHostMallocDefault) != hipSuccess ||
+            hipHostMalloc((void**)&R.total_h, sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
+            return e->fail(KWOK_ENOMEM, "resync staging");
+        memset(R.ctr_h, 0, sizeof(ResyncCounters));
+    }
+    uint8_t*& seen = kind == KWOK_KIND_PODS ? R.pod_seen : R.node_seen;
+    const size_t bytes = kind == KWOK_KIND_PODS ? e->PLa : e->NLa;
+    if (!seen) {  // (zeroed by the allocation)
+        if (int rc = dalloc(e, &seen, bytes)) return rc;
+    } else {
+        HIPCHK(e, hipMemsetAsync(seen, 0, bytes, e->st));
+    }
+    R.open[kind] = true;
+    R.stats[KWOK_RESYNC_STAT_SESSIONS]++;
+    return KWOK_OK;
+}
+
+int kwok_resync_end(kwok_engine* e, int kind) {
+    if (!e || !resync_kind_ok(kind)) return KWOK_EINVAL;
+    e->resync.open[kind] = false;  // (the marks are cleared by the next begin)
+    return KWOK_OK;
+}
+
+int kwok_resync_mark(kwok_engine* e, int kind, const int32_t* handles, size_t n, size_t* n_bad) {
+    if (n_bad) *n_bad = 0;
+    if (!e || !resync_kind_ok(kind) || (n && !handles) || n > 0x7FFFFFF0ull) return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    auto& R = e->resync;
+    if (!R.open[kind]) return e->fail(KWOK_EINVAL, "kwok_resync_mark: no session open");
+    drain(e);  // (a handle is judged against the state after every submitted tick)
+    if (e->poisoned) return poisoned(e);
+    if (!n) return KWOK_OK;
+    if (n > R.mark_cap) {
+        if (R.d_mark) (void)hipFree(R.d_mark);
+        R.d_mark = nullptr, R.mark_cap = 0;
+        const size_t cap = std::max<size_t>(n + n / 4, 4096);
+        if (int rc = dalloc(e, &R.d_mark, cap)) return rc;
+        R.mark_cap = cap;
+    }
+    hipStream_t st = e->st;
+    HIPCHK(e, hipMemcpyAsync(R.d_mark, handles, n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemsetAsync(&R.ctr->bad, 0, sizeof(R.ctr->bad), st));
+    launch_seen_mark_handles(e->S, kind == KWOK_KIND_PODS, R.d_mark, (uint32_t)n, kind == KWOK_KIND_PODS ? R.pod_seen : R.node_seen,
+                             R.ctr, st);
+    HIPCHK(e, hipGetLastError());
+    if (int rc = resync_read_counters(e)) return rc;
+    if (n_bad) *n_bad = (size_t)R.ctr_h->bad;
+    return KWOK_OK;
+}
+
+int kwok_resync_sweep(kwok_engine* e, int kind, int32_t* out_handles, size_t cap, size_t* n_swept, uint32_t* out_released,
+                      int32_t* out_node) {
+    if (n_swept) *n_swept = 0;
+    if (!e || !resync_kind_ok(kind) || (cap && !out_handles)) return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    if (e->multi) return e->fail(KWOK_EINVAL, "kwok_resync_sweep: single-rank engines only");
+    auto& R = e->resync;
+    if (!R.open[kind]) return e->fail(KWOK_EINVAL, "kwok_resync_sweep: no session open");
+    drain(e);  // the device state reflects every submitted tick
+    if (e->poisoned) return poisoned(e);
+    const bool pods = kind == KWOK_KIND_PODS;
+    const uint8_t* seen = pods ? R.pod_seen : R.node_seen;
+    hipStream_t st = e->st;
+    const auto t0 = clk::now();
+    // KWOK_INGEST_PROF: device-side stamps around count + scan and around emit
+    hipEvent_t pev[4] = {};
+    if (e->iprof)
+        for (auto& x : pev) (void)hipEventCreate(&x);
+    struct PevGuard {
+        hipEvent_t* p;
+        ~PevGuard() {
+            for (int k = 0; k < 4; k++)
+                if (p[k]) (void)hipEventDestroy(p[k]);
+        }
+    } pev_guard{pev};
+    auto stamp = [&](int k) {
+        if (pev[k]) (void)hipEventRecord(pev[k], st);
+    };
+    // pass 1: the unmarked live objects per tile, their exclusive prefixes and the total
+    const uint32_t tiles = sweep_tiles(e->S, pods);
+    if (tiles > R.tile_cap) {
+        if (R.tile_cnt) (void)hipFree(R.tile_cnt);
+        if (R.tile_base) (void)hipFree(R.tile_base);
+        R.tile_cnt = R.tile_base = nullptr, R.tile_cap = 0;
+        const size_t tc = std::max<size_t>(tiles + tiles / 4, 1024);
+        int rc = 0;
+        if ((rc = dalloc(e, &R.tile_cnt, tc)) || (rc = dalloc(e, &R.tile_base, tc))) return rc;
+        R.tile_cap = tc;
+    }
+    stamp(0);
+    launch_sweep_count(e->S, pods, seen, R.tile_cnt, st);
+    launch_frame_scan(R.tile_cnt, tiles, R.tile_base, R.total, st);
+    HIPCHK(e, hipGetLastError());
+    stamp(1);
+    HIPCHK(e, hipMemcpyAsync(R.total_h, R.total, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    const uint32_t n = *R.total_h;
+    if (n_swept) *n_swept = n;
+    if (n > cap) return e->fail(KWOK_EINVAL, "kwok_resync_sweep: %u objects to sweep, out_handles holds %zu", n, cap);
+    R.open[kind] = false;  // the sweep closes the session (its DELETE records mark nothing)
+    if (!n) {
+        if (e->iprof) {
+            float cs = 0;
+            (void)hipEventElapsedTime(&cs, pev[0], pev[1]);
+            fprintf(stderr, "[kwok resync] %s: %u tiles, 0 swept: k_sweep_count + k_frame_scan %.3f ms; the call %.3f ms\n",
+                    pods ? "pods" : "nodes", tiles, cs, ms_between(t0, clk::now()));
+        }
+        return KWOK_OK;
+    }
+    if (n > R.out_cap) {
+        if (R.d_handles) (void)hipFree(R.d_handles);
+        if (R.d_nodes) (void)hipFree(R.d_nodes);
+        R.d_handles = R.d_nodes = nullptr, R.out_cap = 0;
+        const size_t oc = std::max<size_t>(n + n / 4, 4096);
+        int rc = 0;
+        if ((rc = dalloc(e, &R.d_handles, oc)) || (rc = dalloc(e, &R.d_nodes, oc))) return rc;
+        R.out_cap = oc;
+    }
+    // pass 2: the DELETE records into the ingest's own record buffer, in slot order; then the ingest's chain
+    // over them, resident (no record or name crosses the link)
+    int rc = pods ? ingest_reserve(e, n, 0) : node_reserve(e, n, 0);
+    if (rc) return rc;
+    stamp(2);
+    launch_sweep_emit(e->S, pods, seen, R.tile_base, n, pods ? e->ing.d_ev : (void*)e->ing.d_nev, R.d_handles, R.d_nodes, st);
+    HIPCHK(e, hipGetLastError());
+    stamp(3);
+    const auto t2 = clk::now();
+    uint64_t released = 0;
+    if (pods) {
+        std::vector<uint32_t> rel_tmp(out_released ? 0 : n);
+        uint32_t* rel = out_released ? out_released : rel_tmp.data();
+        rc = ingest_pods_impl(e, e->ing.d_ev, 1, n, nullptr, 0, nullptr, nullptr, nullptr, rel, true);
+        if (rc >= 0)
+            for (uint32_t i = 0; i < n; i++) released += rel[i] != 0;
+    } else {
+        e->emit_hint = true;
+        e->quiet = 0;
+        e->sum_valid = false;
+        const std::unordered_map<uint32_t, uint32_t> hdoc;
+        const std::vector<kwok_node_event> hrec;
+        const std::vector<std::string> hbuf;
+        const NodeJsonCtx ctx{nullptr, &hdoc, &hrec, &hbuf};
+        ArenaSrc names(e, e->S.node_name);  // the records' name spans index the directory's own names
+        rc = ingest_nodes_impl(e, nullptr, n, nullptr, (size_t)e->NL * NAME_STRIDE, nullptr, nullptr, &ctx);
+    }
+    if (rc < 0) return rc;
+    if (rc > 0) {  // (every record names a live object: none can be rejected)
+        e->poisoned = true;
+        return e->fail(KWOK_EDEVICE, "kwok_resync_sweep: %d of %u DELETE records rejected", rc, n);
+    }
+    HIPCHK(e, hipMemcpyAsync(out_handles, R.d_handles, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (pods && out_node) HIPCHK(e, hipMemcpyAsync(out_node, R.d_nodes, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    R.stats[pods ? KWOK_RESYNC_STAT_SWEPT_PODS : KWOK_RESYNC_STAT_SWEPT_NODES] += n;
+    R.stats[KWOK_RESYNC_STAT_RELEASED] += released;
+    if (e->iprof) {
+        float cs = 0, em = 0;
+        (void)hipEventElapsedTime(&cs, pev[0], pev[1]);
+        (void)hipEventElapsedTime(&em, pev[2], pev[3]);
+        fprintf(stderr, "[kwok resync] %s: %u tiles, %u swept (%llu addresses put back): k_sweep_count + k_frame_scan %.3f ms, "
+                        "k_sweep_emit %.3f ms, apply chain + results %.3f ms; the call %.3f ms\n", pods ? "pods" : "nodes", tiles,
+                n, (unsigned long long)released, cs, em, ms_between(t2, clk::now()), ms_between(t0, clk::now()));
+    }
+    return KWOK_OK;
+}
+
+int kwok_resync_stats(kwok_engine* e, uint64_t out[KWOK_RESYNC_STAT_COUNT]) {
+    if (!e || !out) return KWOK_EINVAL;
+    auto& R = e->resync;
+    if (R.ctr && !e->poisoned)
+        if (int rc = resync_read_counters(e)) return rc;
+    for (int k = 0; k < KWOK_RESYNC_STAT_COUNT; k++) out[k] = R.stats[k];
+    out[KWOK_RESYNC_STAT_MARKED] = R.ctr_h ? (uint64_t)R.ctr_h->marked : 0;
     return KWOK_OK;
 }
 

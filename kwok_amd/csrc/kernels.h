@@ -382,4 +382,26 @@ void launch_node_lookup(const DevState& S, const uint8_t* names, const uint32_t*
 void launch_cni_assign(const DevState& S, const int32_t* handles, const uint32_t* ips, const uint8_t* wr, uint32_t n,
                        int32_t* status, uint32_t* rejected, hipStream_t st);
 
+// ---- relist with Replace (resync.hip, kwok_watch.h): one `seen` byte per pod / node slot ----
+constexpr uint32_t SWEEP_POD_TILE = 2048;   // pod slots per block, tiles laid over whole buckets
+constexpr uint32_t SWEEP_NODE_TILE = 1024;  // node slots per block
+struct ResyncCounters {
+    unsigned long long marked;  // marks stored (records and explicit marks)
+    unsigned long long bad;     // kwok_resync_mark: handles that marked nothing
+};
+// the batch's UPSERT records whose final status is KWOK_OK mark their handle's slot (after the
+// apply pass; a speculative pass that returned for growth marks nothing: the redo does)
+void launch_seen_mark_pods(const DevState& S, const IngestBatch& I, uint8_t* seen, ResyncCounters* rc, hipStream_t st);
+void launch_seen_mark_nodes(const DevState& S, const NodeBatch& N, uint8_t* seen, ResyncCounters* rc, hipStream_t st);
+// kwok_resync_mark: handles of live objects (PS_USED / NS_SLOT) mark their slot, any other counts in rc->bad
+void launch_seen_mark_handles(const DevState& S, int pods, const int32_t* handles, uint32_t n, uint8_t* seen,
+                              ResyncCounters* rc, hipStream_t st);
+uint32_t sweep_tiles(const DevState& S, int pods);
+// per tile: the live objects without a mark
+void launch_sweep_count(const DevState& S, int pods, const uint8_t* seen, uint32_t* tile_cnt, hipStream_t st);
+// ... and their DELETE records (pods: kwok_pod_rec with the held address; nodes: kwok_node_event whose name
+// spans index S.node_name), handles and (pods) node handles at tile_base + rank, in slot order (k < n_out)
+void launch_sweep_emit(const DevState& S, int pods, const uint8_t* seen, const uint32_t* tile_base, uint32_t n_out, void* recs,
+                       int32_t* handles, int32_t* nodes, hipStream_t st);
+
 }  // namespace kwok

@@ -120,6 +120,11 @@ def declare(lib, pre):
             "frame_list": (C.c_int, [VP, SZ, VP, SZ, P(SZ), VP]),
             "frame_list_gpu": (C.c_int, [VP, VP, SZ, VP, SZ, P(SZ), VP, P(SZ), P(U64)]),
             "list_stats": (C.c_int, [VP, VP]),
+            "resync_begin": (C.c_int, [VP, C.c_int]),
+            "resync_mark": (C.c_int, [VP, C.c_int, VP, SZ, P(SZ)]),
+            "resync_sweep": (C.c_int, [VP, C.c_int, VP, SZ, P(SZ), VP, VP]),
+            "resync_end": (C.c_int, [VP, C.c_int]),
+            "resync_stats": (C.c_int, [VP, VP]),
         })
     for name, (res, args) in sig.items():
         f = getattr(lib, pre + name, None)
@@ -653,6 +658,54 @@ class Engine(EngineBase):
         out = (C.c_uint64 * len(abi.LIST_STATS))()
         self._check(self._lib.kwok_list_stats(self._h, out), "list_stats")
         return dict(zip(abi.LIST_STATS, list(out)))
+
+    # ---- relist with Replace (include/kwok_watch.h): a resync session per kind ----
+    def resync_begin(self, kind):
+        """kwok_resync_begin: open the kind's (abi.KIND_NODES / KIND_PODS) session, marks cleared"""
+        self._check(self._lib.kwok_resync_begin(self._h, kind), "resync_begin")
+
+    def resync_mark(self, kind, handles):
+        """kwok_resync_mark: mark objects seen in the list but not ingested -> the handles that marked nothing"""
+        hs = np.ascontiguousarray(handles, np.int32)
+        bad = C.c_size_t()
+        self._check(self._lib.kwok_resync_mark(self._h, kind, hs.ctypes.data, len(hs), C.byref(bad)), "resync_mark")
+        return bad.value
+
+    def resync_sweep(self, kind, cap=None):
+        """kwok_resync_sweep: remove every live object of the kind without a mark and close
+        the session -> (handles ascending, released addresses, node handles); the last two
+        are None for nodes.  cap: the room for handles (default: sized from a first, refused
+        call; KwokError(EINVAL) with .n_swept set when a given cap is too small)."""
+        pods = kind == abi.KIND_PODS
+        n = C.c_size_t()
+        if cap is None:
+            rc = self._lib.kwok_resync_sweep(self._h, kind, None, 0, C.byref(n), None, None)
+            if rc == abi.OK or n.value == 0:  # nothing to sweep (session closed), or an error of the call
+                self._check(rc, "resync_sweep")
+                return np.empty(0, np.int32), (np.empty(0, np.uint32) if pods else None), (np.empty(0, np.int32) if pods else None)
+            cap = n.value
+        hs = np.empty(max(cap, 1), np.int32)
+        rel = np.zeros(max(cap, 1), np.uint32) if pods else None
+        nd = np.empty(max(cap, 1), np.int32) if pods else None
+        rc = self._lib.kwok_resync_sweep(self._h, kind, hs.ctypes.data, cap, C.byref(n),
+                                         rel.ctypes.data if pods else None, nd.ctypes.data if pods else None)
+        try:
+            self._check(rc, "resync_sweep")
+        except KwokError as err:
+            err.n_swept = n.value
+            raise
+        k = n.value
+        return hs[:k], (rel[:k] if pods else None), (nd[:k] if pods else None)
+
+    def resync_end(self, kind):
+        """kwok_resync_end: close the kind's session without sweeping"""
+        self._check(self._lib.kwok_resync_end(self._h, kind), "resync_end")
+
+    def resync_stats(self):
+        """kwok_resync_stats: sessions begun / marks stored / nodes swept / pods swept / addresses put back"""
+        out = (C.c_uint64 * len(abi.RESYNC_STATS))()
+        self._check(self._lib.kwok_resync_stats(self._h, out), "resync_stats")
+        return dict(zip(abi.RESYNC_STATS, list(out)))
 
     @staticmethod
     def _arena_arg(arena):
