@@ -230,6 +230,71 @@ enum {
 };
 int kwok_resync_stats(kwok_engine* e, uint64_t out[KWOK_RESYNC_STAT_COUNT]);
 
+/* ---- Pod uid directory ------------------------------------------
+ *
+ * metadata.uid -> pod handle, kept on the device.  With it enabled a framed pod
+ * batch needs no handle[] from the caller: kwok_ingest_pods_framed_uid resolves
+ * every frame's uid, cuts the batch into runs and binds the pods it creates, all on
+ * the device.  The yardstick is the host path, record for record: the batch cut into
+ * runs in which no new pod appears twice, each run through kwok_ingest_pods_framed
+ * with handles from a uid -> handle map of the caller (controller.ingest_pod_runs).
+ *
+ * Rules:
+ *   - a run resolves every record of its range before any of them is applied: a
+ *     Deleted and an Added of one known uid in one run both carry its handle;
+ *   - cuts are positional.  In the current range [lo, n), `created` is the set of
+ *     uids the directory does not hold that appear in a non-DELETED record; the run
+ *     ends before the first record whose uid an earlier record put into `created`,
+ *     and everything from there on (records of other pods included) waits for the
+ *     next run, which resolves again.  *n_runs counts the runs that sent a record;
+ *   - a DELETED frame of a uid that resolves to nothing (a pod the tick or a sweep
+ *     already removed included): KWOK_NOT_SENT, handle -1, nothing changes;
+ *   - a non-DELETED record that ended KWOK_OK binds its uid to the handle it
+ *     returned; any other status binds nothing (a failed create's uid is new again);
+ *   - a frame with KWOK_FRAME_ESC_UID, or whose uid is empty or longer than
+ *     KWOK_UID_MAX: KWOK_EDOMAIN, handle -1, nothing changes (never guessed or
+ *     truncated);
+ *   - a frame out of range, not KWOK_OK or of type NONE / BOOKMARK / ERROR:
+ *     KWOK_EINVAL, as kwok_ingest_pods_framed;
+ *   - a binding ends with its pod: whatever frees the slot (a Deleted event, the
+ *     engine's tick, a sweep) unbinds the uid.  A pod created through an entry that
+ *     carries no uid (typed events, records, kwok_ingest_pods_framed) has none
+ *     until kwok_uid_bind names it;
+ *   - single-rank engines only (a rank does not see other ranks' pods): enable is
+ *     refused with KWOK_EINVAL on a multi-rank engine. */
+#define KWOK_UID_MAX 40  /* a Kubernetes uid is a 36-byte UUID */
+#define KWOK_NOT_SENT 1  /* per-record status: a Deleted event of a pod the engine does not hold */
+/* Allocates the directory (idempotent).  Pods that exist have no uid until bound. */
+int kwok_uid_dir_enable(kwok_engine* e);
+/* uid i = arena[off[i], +len[i]) becomes the uid of live pod handles[i] (rebinding replaces it).
+ * Counted in *n_bad, binding nothing: a handle out of range, in a bucket this rank does not
+ * own or on an unused slot, a uid that is empty or longer than KWOK_UID_MAX.  One handle
+ * named twice in a call keeps either uid. */
+int kwok_uid_bind(kwok_engine* e, const int32_t* handles, const char* arena, const uint64_t* off, const uint32_t* len,
+                  size_t n, size_t* n_bad);
+/* out_handles[i]: the live pod bound to uid i, or -1.  Drains submitted ticks first. */
+int kwok_uid_lookup(kwok_engine* e, const char* arena, const uint64_t* off, const uint32_t* len, size_t n,
+                    int32_t* out_handles);
+/* kwok_ingest_pods_framed without handle[] (rules above).  *n_host: documents the host
+ * codec decided; *n_runs: the runs.  KWOK_EINVAL for the call when the directory is not
+ * enabled or stream_id is not the resident stream.  Returns the number of records whose
+ * status is neither KWOK_OK nor KWOK_NOT_SENT, or an error. */
+int kwok_ingest_pods_framed_uid(kwok_engine* e, const kwok_codec* c, uint64_t stream_id, const uint32_t* frame_idx,
+                                size_t n, int32_t* out_handles, int32_t* out_status, uint32_t* out_released,
+                                size_t* n_host, size_t* n_runs);
+enum {
+    KWOK_UID_STAT_LOOKUPS = 0,   /* keyable uids probed (framed records and kwok_uid_lookup) */
+    KWOK_UID_STAT_HITS,          /* ... that resolved to a live pod */
+    KWOK_UID_STAT_BINDS,         /* creates noted plus explicit binds */
+    KWOK_UID_STAT_UNBOUND,       /* creates through entries that carry no uid */
+    KWOK_UID_STAT_RUNS,          /* runs that sent a record */
+    KWOK_UID_STAT_CUTS,          /* run cuts */
+    KWOK_UID_STAT_REBUILDS,      /* table rebuilds */
+    KWOK_UID_STAT_TABLE_ENTRIES, /* entries the table holds, stale ones included */
+    KWOK_UID_STAT_COUNT
+};
+int kwok_uid_stats(kwok_engine* e, uint64_t out[KWOK_UID_STAT_COUNT]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,7 @@ import (
 	"net"
 	"unsafe"
 
+	"k8s.io/apimachinery/pkg/types"
 	"sigs.k8s.io/kwok/pkg/kwok/controllers/templates"
 )
 
@@ -576,6 +577,74 @@ func (g *gpuEngine) ingestPodsFramed(codec *gpuCodec, streamID uint64, idx []uin
 		err = fmt.Errorf("kwok_ingest_pods_framed: %d: %s", int(rc), g.lastError())
 	}
 	return
+}
+
+// ---- the pod uid directory (kwok_watch.h, DESIGN.md §23): metadata.uid -> handle on the device ----
+
+// uidDirEnable: kwok_uid_dir_enable (idempotent; single-rank engines only)
+func (g *gpuEngine) uidDirEnable() error {
+	if rc := C.kwok_uid_dir_enable(g.h); rc != C.KWOK_OK {
+		return fmt.Errorf("kwok_uid_dir_enable: %d: %s", int(rc), g.lastError())
+	}
+	return nil
+}
+
+// uidSpans: the uids back to back in one arena, with their offsets and lengths
+func uidSpans(uids []types.UID) (arena []byte, offs []uint64, lens []uint32) {
+	offs, lens = make([]uint64, len(uids)), make([]uint32, len(uids))
+	for i, u := range uids {
+		offs[i], lens[i] = uint64(len(arena)), uint32(len(u))
+		arena = append(arena, u...)
+	}
+	return append(arena, 0), offs, lens
+}
+
+// uidBind: kwok_uid_bind - uids[i] becomes the uid of live pod handles[i]; returns the records that bound nothing
+func (g *gpuEngine) uidBind(handles []int32, uids []types.UID) (int, error) {
+	if len(handles) == 0 {
+		return 0, nil
+	}
+	arena, offs, lens := uidSpans(uids)
+	var bad C.size_t
+	rc := C.kwok_uid_bind(g.h, (*C.int32_t)(&handles[0]), (*C.char)(unsafe.Pointer(&arena[0])), (*C.uint64_t)(&offs[0]),
+		(*C.uint32_t)(&lens[0]), C.size_t(len(handles)), &bad)
+	if rc < 0 {
+		return 0, fmt.Errorf("kwok_uid_bind: %d: %s", int(rc), g.lastError())
+	}
+	return int(bad), nil
+}
+
+// uidLookup: kwok_uid_lookup - the handle of the live pod bound to each uid, or -1
+func (g *gpuEngine) uidLookup(uids []types.UID) ([]int32, error) {
+	out := make([]int32, len(uids))
+	if len(uids) == 0 {
+		return out, nil
+	}
+	arena, offs, lens := uidSpans(uids)
+	rc := C.kwok_uid_lookup(g.h, (*C.char)(unsafe.Pointer(&arena[0])), (*C.uint64_t)(&offs[0]), (*C.uint32_t)(&lens[0]),
+		C.size_t(len(uids)), (*C.int32_t)(&out[0]))
+	if rc < 0 {
+		return nil, fmt.Errorf("kwok_uid_lookup: %d: %s", int(rc), g.lastError())
+	}
+	return out, nil
+}
+
+// ingestPodsFramedUID: kwok_ingest_pods_framed_uid - ingestPodsFramed without the handle array: the uids are
+// resolved, the runs cut and the creates bound on the device.  status[i] may be C.KWOK_NOT_SENT
+func (g *gpuEngine) ingestPodsFramedUID(codec *gpuCodec, streamID uint64, idx []uint32) (handles, status []int32, runs int, err error) {
+	n := len(idx)
+	handles, status = make([]int32, n), make([]int32, n)
+	if n == 0 {
+		return
+	}
+	released := make([]uint32, n)
+	var nh, nr C.size_t
+	rc := C.kwok_ingest_pods_framed_uid(g.h, codec.c, C.uint64_t(streamID), (*C.uint32_t)(&idx[0]), C.size_t(n),
+		(*C.int32_t)(&handles[0]), (*C.int32_t)(&status[0]), (*C.uint32_t)(&released[0]), &nh, &nr)
+	if rc < 0 {
+		err = fmt.Errorf("kwok_ingest_pods_framed_uid: %d: %s", int(rc), g.lastError())
+	}
+	return handles, status, int(nr), err
 }
 
 // poolPut replicates IPs another rank released at ingest time (multi-GPU).

@@ -186,6 +186,10 @@ type GPUController struct {
 	podUID   map[int32]types.UID // pod handle -> UID (the reverse of podByUID)
 	podRef   map[int32]types.NamespacedName
 
+	// byUID (KWOK_UID_DIR=1): the engine's pod uid directory (kwok_watch.h, DESIGN.md §23) holds uid -> handle;
+	// podByUID is then a batch-local map filled by kwok_uid_lookup, and List pages go through
+	// kwok_ingest_pods_framed_uid.  podUID / podRef (handle -> uid / name, for addressing patches) stay
+	byUID       bool
 	gpuCodec    bool // pod documents decoded on the GPU (kwok_ingest_pods_json); KWOK_GPU_CODEC=0: the host codec
 	podDocsHost int  // pod documents the GPU codec left to the host codec (logged)
 	nodeDocsHost int // node documents the GPU codec left to the host codec (logged)
@@ -205,7 +209,16 @@ func newGPUController(conf Config, interval time.Duration) (*GPUController, erro
 		eng.close()
 		return nil, err
 	}
+	byUID := os.Getenv("KWOK_UID_DIR") == "1"
+	if byUID {
+		if err := eng.uidDirEnable(); err != nil {
+			codec.close()
+			eng.close()
+			return nil, err
+		}
+	}
 	return &GPUController{
+		byUID: byUID,
 		conf: conf, eng: eng, codec: codec, interval: interval, finalizer: finalizerPatch(),
 		nodeName: map[int32]string{}, nodeHandle: map[string]int32{}, podByUID: map[types.UID]int32{},
 		podUID: map[int32]types.UID{},
@@ -287,7 +300,7 @@ func (c *GPUController) listInto(ctx context.Context, nodes bool, opt metav1.Lis
 		for i := range frames {
 			f := &frames[i]
 			h := int32(-1)
-			if !nodes {
+			if !nodes && !c.byUID {
 				uid, err := text(staged, f.uid, f.flags&C.KWOK_FRAME_ESC_UID != 0)
 				if err != nil {
 					return "", err
@@ -301,6 +314,8 @@ func (c *GPUController) listInto(ctx context.Context, nodes bool, opt metav1.Lis
 		var out, ss []int32
 		if nodes {
 			out, ss, err = c.eng.ingestNodesFramed(c.codec, sid, idx)
+		} else if c.byUID { // uids resolved and creates bound on the device: no handle array, no map
+			out, ss, _, err = c.eng.ingestPodsFramedUID(c.codec, sid, idx)
 		} else {
 			out, ss, err = c.eng.ingestPodsFramed(c.codec, sid, idx, hs)
 		}
@@ -326,7 +341,9 @@ func (c *GPUController) listInto(ctx context.Context, nodes bool, opt metav1.Lis
 				return "", err
 			}
 			uid, _ := text(staged, f.uid, f.flags&C.KWOK_FRAME_ESC_UID != 0)
-			c.podByUID[types.UID(uid)] = out[k]
+			if !c.byUID {
+				c.podByUID[types.UID(uid)] = out[k]
+			}
 			c.podUID[out[k]] = types.UID(uid)
 			c.podRef[out[k]] = types.NamespacedName{Namespace: ns, Name: name}
 		}
@@ -737,9 +754,27 @@ func (c *GPUController) flushPods(ctx context.Context, tasks *parallelTasks, b o
 		return nil
 	}
 	if !c.gpuCodec {
+		if c.byUID { // (the same bracket as below around the host-codec runs)
+			if err := c.lookupBatch(b.uids); err != nil {
+				return err
+			}
+			defer func() { c.podByUID = map[types.UID]int32{} }()
+			if err := c.flushPodsHost(ctx, tasks, b); err != nil {
+				return err
+			}
+			return c.bindBatch()
+		}
 		return c.flushPodsHost(ctx, tasks, b)
 	}
 	logger := log.FromContext(ctx)
+	if c.byUID {
+		// the batch's uids resolved by the device: podByUID holds this batch's known pods only, the runs
+		// below update it, and the pods it ends with are bound (typed events and raw bytes of one pod mix)
+		if err := c.lookupBatch(b.uids); err != nil {
+			return err
+		}
+		defer func() { c.podByUID = map[types.UID]int32{} }()
+	}
 	var run []int
 	created := map[types.UID]bool{} // new pods of the current run
 	flush := func() error {
@@ -813,7 +848,49 @@ func (c *GPUController) flushPods(ctx context.Context, tasks *parallelTasks, b o
 		}
 		run = append(run, i)
 	}
-	return flush()
+	if err := flush(); err != nil {
+		return err
+	}
+	if c.byUID {
+		return c.bindBatch()
+	}
+	return nil
+}
+
+// lookupBatch (byUID): podByUID = the batch's uids the directory holds (kwok_uid_lookup)
+func (c *GPUController) lookupBatch(uids []types.UID) error {
+	seen := map[types.UID]struct{}{}
+	us := make([]types.UID, 0, len(uids))
+	for _, u := range uids {
+		if _, ok := seen[u]; !ok {
+			seen[u] = struct{}{}
+			us = append(us, u)
+		}
+	}
+	hs, err := c.eng.uidLookup(us)
+	if err != nil {
+		return err
+	}
+	c.podByUID = map[types.UID]int32{}
+	for i, u := range us {
+		if hs[i] >= 0 {
+			c.podByUID[u] = hs[i]
+		}
+	}
+	return nil
+}
+
+// bindBatch (byUID): the pods the batch-local map ends with are bound on the device (kwok_uid_bind); a uid
+// the directory cannot key (empty, longer than KWOK_UID_MAX) is left out and stays unknown to it
+func (c *GPUController) bindBatch() error {
+	hs, us := make([]int32, 0, len(c.podByUID)), make([]types.UID, 0, len(c.podByUID))
+	for u, h := range c.podByUID {
+		if len(u) > 0 && len(u) <= C.KWOK_UID_MAX {
+			hs, us = append(hs, h), append(us, u)
+		}
+	}
+	_, err := c.eng.uidBind(hs, us)
+	return err
 }
 
 // flushPodsHost: flushPods with the host codec (kwok_decode_pods) and the packed

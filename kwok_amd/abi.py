@@ -119,6 +119,10 @@ LIST_STATS = ("bodies", "items", "host_items", "host_bodies", "body_bytes")  # K
 KIND_NODES, KIND_PODS = 0, 1  # KWOK_KIND_*: the kind of a resync session (relist with Replace)
 RESYNC_STATS = ("sessions", "marked", "swept_nodes", "swept_pods", "released")  # KWOK_RESYNC_STAT_* order
 
+UID_MAX = 40   # KWOK_UID_MAX: the longest uid the pod uid directory keys
+NOT_SENT = 1   # KWOK_NOT_SENT: a Deleted event of a pod the engine does not hold (controller.NOT_SENT)
+UID_STATS = ("lookups", "hits", "binds", "unbound", "runs", "cuts", "rebuilds", "table_entries")  # KWOK_UID_STAT_* order
+
 
 class ListInfo(C.Structure):
     """kwok_list_info: the envelope of a List body (offsets into the body)"""

@@ -309,8 +309,12 @@ class Controller:
                     max_pod_specs=4096)
 
     def __init__(self, conf: Config, backend=None, codec_threads=1, suppress_echoes=True, geometry=None,
-                 gpu_codec=True):
+                 gpu_codec=True, uid_directory=False):
         self.conf = conf
+        # uid_directory: the engine's pod uid directory (kwok_watch.h) resolves metadata.uid -> handle on
+        # the device; pod_by_uid stays empty (a uid the directory cannot key - empty, escaped in the
+        # stream, longer than abi.UID_MAX - is rejected with KWOK_EDOMAIN, where the map would take it)
+        self.uid_dir = bool(uid_directory)
         self.suppress = suppress_echoes  # False: every echo re-ingested (tests: the A/B that echoes change nothing)
         custom = {}
         if conf.pod_status_template is not None:
@@ -324,6 +328,10 @@ class Controller:
         cfg = make_config(cidr=conf.cidr, node_ip=conf.node_ip, start_time=conf.start_time,
                           enable_cni=conf.enable_cni, heartbeat_once=True, **geo, **custom)
         self.eng = (backend or Engine)(cfg)
+        if self.uid_dir:
+            if not hasattr(self.eng, "uid_dir_enable"):
+                raise ValueError("uid_directory needs the engine backend (kwok_uid_dir_enable)")
+            self.eng.uid_dir_enable()
         self.codec = Codec(manage_all_nodes=conf.manage_all_nodes,
                            manage_nodes_with_annotation_selector=conf.manage_nodes_with_annotation_selector,
                            manage_nodes_with_label_selector=conf.manage_nodes_with_label_selector,
@@ -538,6 +546,24 @@ class Controller:
             sid = self.spec_ids[spec] = self.eng.register_pod_spec(*spec)
         return sid
 
+    def _uid_map(self, uids):
+        """the typed paths' uid -> handle map: the controller's own, or (uid_directory) the batch's
+        uids resolved by the device (kwok_uid_lookup) - the pods the directory holds"""
+        if not self.uid_dir:
+            return self.pod_by_uid
+        us = list(dict.fromkeys(uids))
+        hs = self.eng.uid_lookup(us) if us else []
+        return {u: int(h) for u, h in zip(us, hs) if h >= 0}
+
+    def _uid_bind(self, by_uid, uids):
+        """uid_directory: the pods a typed batch created (or touched) are bound on the device, so that
+        raw bytes and typed events of one pod can be mixed"""
+        if not self.uid_dir:
+            return
+        us = [u for u in dict.fromkeys(uids) if u in by_uid and 0 < len(u.encode()) <= abi.UID_MAX]
+        if us:
+            self.eng.uid_bind([by_uid[u] for u in us], us)
+
     def _flush_pods(self, batch):
         """gpu_controller.go flushPods: decode, then ingest in runs (ingest_pod_runs).
         On the HIP engine the documents are decoded on the GPU (ingest_doc_runs);
@@ -576,7 +602,9 @@ class Controller:
         uids = [ws[i].uid for i in idx]
         deleted = [ws[i].deleted for i in idx]
         refs = [(b.text(b.pods[i].namespace_), b.text(b.pods[i].name)) for i in idx]
-        hs, st, runs = ingest_pod_runs(self.eng, self.pod_by_uid, recs, uids, deleted, bytes(b.buf))
+        by_uid = self._uid_map(uids)
+        hs, st, runs = ingest_pod_runs(self.eng, by_uid, recs, uids, deleted, bytes(b.buf))
+        self._uid_bind(by_uid, uids)
         self.stats.pod_records += int((st != NOT_SENT).sum())
         self.stats.pod_runs += runs
         for k in range(len(recs)):
@@ -595,7 +623,9 @@ class Controller:
         kwok_ingest_pods_json in runs; names and nodes from the watch objects"""
         uids = [w.uid for w in ws]
         deleted = [w.deleted for w in ws]
-        hs, st, runs, n_host = ingest_doc_runs(self.eng, self.codec, self.pod_by_uid, docs, uids, deleted)
+        by_uid = self._uid_map(uids)
+        hs, st, runs, n_host = ingest_doc_runs(self.eng, self.codec, by_uid, docs, uids, deleted)
+        self._uid_bind(by_uid, uids)
         self.stats.pod_records += int((st != NOT_SENT).sum())
         self.stats.pod_runs += runs
         self.stats.pod_docs_host += n_host
@@ -719,7 +749,8 @@ class Controller:
             if self.suppress and not dl and self.echo.is_echo(uid, rv) and uid not in seen:
                 self.stats.echoes_at_flush += 1
                 if sess is not None:  # seen in the list, not ingested: marked by its known handle
-                    echoed.append(self.node_handle.get(name(i), -1) if nodes else self.pod_by_uid.get(uid, -1))
+                    echoed.append(self.node_handle.get(name(i), -1) if nodes else
+                                  uid if self.uid_dir else self.pod_by_uid.get(uid, -1))
                 continue
             seen.add(uid)
             if dl:
@@ -727,6 +758,8 @@ class Controller:
             keep.append(i)
             uids.append(uid)
             deleted.append(dl)
+        if echoed and not nodes and self.uid_dir:  # (the echoes' handles from the device)
+            echoed = self.eng.uid_lookup(echoed).tolist()
         echoed = [h for h in echoed if h >= 0]
         if echoed:
             self.eng.resync_mark(abi.KIND_NODES if nodes else abi.KIND_PODS, echoed)
@@ -761,7 +794,11 @@ class Controller:
             n_host[0] += nh
             return h1, s1
 
-        hs, st, runs = ingest_pod_runs(self.eng, self.pod_by_uid, np.empty(len(keep)), uids, deleted, None, sender=send)
+        if self.uid_dir:  # one call: uids resolved, runs cut and creates bound on the device
+            hs, st, _rel, nh, runs = self.eng.ingest_pods_framed_uid(self.codec, sid, keep)
+            n_host[0] = nh
+        else:
+            hs, st, runs = ingest_pod_runs(self.eng, self.pod_by_uid, np.empty(len(keep)), uids, deleted, None, sender=send)
         self.stats.pod_records += int((st != NOT_SENT).sum())
         self.stats.pod_runs += runs
         self.stats.pod_docs_host += n_host[0]

@@ -318,6 +318,28 @@ struct NodeSummary {
     uint32_t freed, created, pad[2];
 };
 
+// ---- the pod uid directory (uid.hip) ---------------------------------------------
+// the class k_uid_resolve gives a record of a by-uid framed batch
+enum : uint8_t {
+    UID_HIT = 0,       // the directory holds the uid: the record carries that pod's handle
+    UID_NEW,           // a non-DELETED frame of an unknown uid: a create (handle -1)
+    UID_NOT_SENT,      // a DELETED frame of an unknown uid: withheld, KWOK_NOT_SENT
+    UID_DOMAIN,        // a uid the device cannot key exactly: withheld, KWOK_EDOMAIN
+    UID_INVALID,       // no ingestible frame: withheld, KWOK_EINVAL
+};
+struct UidCounters {   // device memory, read back by the host
+    unsigned long long lookups, hits, binds, unbound;
+    unsigned long long bad;      // kwok_uid_bind: records that bound nothing (reset per call)
+    unsigned long long entries;  // table entries written since the table was last cleared
+    uint32_t err, pad;           // a probe wrapped the whole table
+};
+struct UidRun {        // per run of a by-uid batch, read back by the host
+    uint32_t first_cut;  // the first record that waits for the next run (reset to ~0)
+    uint32_t n_sent;     // records of the range that reach the decode
+    uint32_t n_new;      // ... of them creates (each inserts one table entry)
+    uint32_t pad;
+};
+
 // spec descriptor: A | B | C segments of the pod patch (see templates.cpp)
 struct SpecDesc {
     uint32_t off;             // into the spec byte array (timestamp slots zero)

@@ -296,6 +296,44 @@ struct kwok_engine {
         uint64_t stats[KWOK_RESYNC_STAT_COUNT] = {};
     } resync;
 
+    // ---- the pod uid directory (uid.hip, kwok_watch.h): a uid per pod slot, the table
+    // of hints, the per-call buffers of a by-uid framed batch and of bind / lookup ----
+    struct Uid {
+        struct Bytes {
+            uint8_t b[KWOK_UID_MAX];
+        };
+        bool on = false;
+        Bytes* pod_uid = nullptr;        // [PLa] re-laid out with the pod arrays (grow_pods)
+        uint8_t* pod_uid_len = nullptr;  // [PLa]
+        unsigned long long* tab = nullptr;
+        size_t tab_cap = 0;              // entries (a power of two)
+        int forced_log2 = 0;             // KWOK_UID_TAB_LOG2 (tests)
+        uint64_t live = 0, inserted = 0; // entries at the last rebuild; an upper bound of the inserts since
+        UidCounters* ctr = nullptr;      // device
+        UidCounters* ctr_h = nullptr;    // pinned
+        UidRun* run = nullptr;           // device
+        UidRun* run_h = nullptr;         // pinned
+        // per record of a by-uid batch
+        size_t cap = 0;
+        uint32_t *fidx = nullptr, *uoff = nullptr, *res_rel = nullptr;
+        uint8_t *ulen = nullptr, *cls = nullptr;
+        uint64_t* hash = nullptr;
+        int32_t *res_h = nullptr, *res_st = nullptr;
+        uint32_t* claim = nullptr;
+        size_t claim_cap = 0;
+        // bind / lookup: handles or results, spans, the caller's arena
+        size_t qcap = 0, acap = 0;
+        int32_t* q_h = nullptr;
+        uint64_t* q_off = nullptr;
+        uint32_t* q_len = nullptr;
+        uint8_t* q_arena = nullptr;
+        // the by-uid batch whose records the ingest is applying (null: an entry that carries no uid)
+        const UidNote* note = nullptr;
+        std::vector<hipEvent_t> note_ev;  // KWOK_INGEST_PROF: stamps around each k_uid_note of a by-uid batch, in pairs
+        uint64_t stats[KWOK_UID_STAT_COUNT] = {};
+        UidDir dir() const { return UidDir{reinterpret_cast<uint8_t*>(pod_uid), pod_uid_len, tab, (uint32_t)(tab_cap - 1), ctr}; }
+    } uid;
+
     // ---- the pod codec on the GPU (json.hip): per-document buffers, the codec's
     // selectors, the spec table (kwok_spec_key -> spec id) ----
     struct Json {
@@ -577,6 +615,11 @@ int dalloc(kwok_engine* e, T** p, size_t n) {
     r = hipMemsetAsync(*p, 0, bytes, e->st);
     if (r != hipSuccess) return e->fail(KWOK_EDEVICE, "hipMemset: %s", hipGetErrorString(r));
     return KWOK_OK;
+}
+template <class T>
+void dfree(T*& p) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
 }
 
 // grow a device buffer to hold `bytes` (keeps contents)
@@ -899,6 +942,9 @@ int grow_pods(kwok_engine* e, uint32_t new_cp) {
         (rc = resize(S.alloc_addr, false)) || (rc = resize(S.use_list, false)) || (rc = resize(S.rel_list, false)))
         return rc;
     if (e->resync.pod_seen && (rc = relayout(e->resync.pod_seen))) return rc;  // (a growth inside a session keeps the marks)
+    // the uid directory's per-slot uids move with their pods (handles are stable; the table is rebuilt
+    // to the new size before its next use, uid_ensure)
+    if (e->uid.on && ((rc = relayout(e->uid.pod_uid)) || (rc = relayout(e->uid.pod_uid_len)))) return rc;
     for (auto& T : e->slots) {
         if (!T.alloc) continue;
         if ((rc = resize(T.pp_pods, true)) || (rc = resize(T.pp_off, true)) || (rc = resize(T.pp_len, true)) ||
@@ -1233,6 +1279,15 @@ void kwok_engine_destroy(kwok_engine* e) {
             if (p) (void)hipFree(p);
         if (R.ctr_h) (void)hipHostFree(R.ctr_h);
         if (R.total_h) (void)hipHostFree(R.total_h);
+    }
+    {
+        auto& U = e->uid;
+        void* up[] = {U.pod_uid, U.pod_uid_len, U.tab, U.ctr, U.run, U.fidx, U.uoff, U.res_rel, U.ulen, U.cls, U.hash,
+                      U.res_h, U.res_st, U.claim, U.q_h, U.q_off, U.q_len, U.q_arena};
+        for (void* p : up)
+            if (p) (void)hipFree(p);
+        if (U.ctr_h) (void)hipHostFree(U.ctr_h);
+        if (U.run_h) (void)hipHostFree(U.run_h);
     }
     if (e->h_xall) (void)hipHostFree(e->h_xall);
     if (e->pinned) (void)hipHostFree(e->pinned);
@@ -2139,6 +2194,28 @@ int ingest_pods_impl(kwok_engine* e, const void* recs, int packed, size_t n, con
         HIPCHK(e, hipGetLastError());
         return KWOK_OK;
     };
+    // the uid directory, while enabled: behind the apply pass of every pod chunk its creates take their
+    // uid (a by-uid batch: and a table entry) or lose the slot's previous one (k: the chunk)
+    auto note_uid = [&](IngestBatch I, bool spec, uint32_t k) -> int {
+        if (!e->uid.on) return KWOK_OK;
+        I.spec = spec ? 1u : 0u;
+        UidNote N{};
+        if (e->uid.note) {
+            const size_t lo = lo_of(k);
+            N = *e->uid.note;
+            N.uoff += lo, N.ulen += lo, N.hash += lo, N.cls += lo;
+        }
+        hipEvent_t pe[2] = {};
+        if (e->iprof && e->uid.note && hipEventCreate(&pe[0]) == hipSuccess && hipEventCreate(&pe[1]) == hipSuccess) {
+            e->uid.note_ev.push_back(pe[0]);
+            e->uid.note_ev.push_back(pe[1]);
+            (void)hipEventRecord(pe[0], st);
+        }
+        launch_uid_note(e->S, I, e->uid.dir(), N, st);
+        if (pe[1]) (void)hipEventRecord(pe[1], st);
+        HIPCHK(e, hipGetLastError());
+        return KWOK_OK;
+    };
     int tick_k = -1;  // tick mode: the slot of the tick queued behind the batch
     auto run = [&]() -> int {
         HIPCHK(e, hipEventRecord(G.go, st));
@@ -2158,6 +2235,7 @@ int ingest_pods_impl(kwok_engine* e, const void* recs, int packed, size_t n, con
             if (int r = enqueue_sort_need(e, I)) return r;
             if (int r = enqueue_apply(e, I, true)) return r;
             if (int r = mark_seen(I, true)) return r;
+            if (int r = note_uid(I, true, k)) return r;
             if (tstamp) HIPCHK(e, hipEventRecord(G.tev[4 + k], st));  // 4 / 5: chunk k applied
             // chunk k's results on the results stream; its accumulator set free for chunk k + 2
             HIPCHK(e, hipEventRecord(G.used[k & 1], st));
@@ -2229,6 +2307,7 @@ int ingest_pods_impl(kwok_engine* e, const void* recs, int packed, size_t n, con
             const int r = ingest_chunk(e, chunk_batch(k));
             if (r < 0) return r;
             if (int r2 = mark_seen(chunk_batch(k), false)) return r2;
+            if (int r2 = note_uid(chunk_batch(k), false, k)) return r2;
             if (e->debug_fail_apply == k + 1)
                 return e->fail(KWOK_EDEVICE, "injected failure after the apply pass of ingest chunk %u", k);
             rejected += r;
@@ -2387,9 +2466,11 @@ int json_reserve(kwok_engine* e, size_t n) {
 // returns the number of documents listed for the host (JSON_HOST / JSON_SPEC)
 int json_decode(kwok_engine* e, const kwok_codec* c, const char* arena, size_t arena_len, const uint64_t* doc_off,
                 const uint32_t* doc_len, size_t n, const uint8_t* op, const int32_t* handle, uint32_t* n_host,
-                const uint8_t* resident = nullptr) {
+                const uint8_t* resident = nullptr, bool dev_inputs = false) {
     // resident: the documents are on the device already, at this address (the watch
     // stream, kwok_ingest_pods_framed): nothing is copied, one decode launch
+    // dev_inputs (with resident): the spans, ops and handles are in the codec's device
+    // buffers already (k_uid_resolve wrote them); the four host arrays are not read
     auto& G = e->ing;
     auto& J = e->json;
     hipStream_t st = e->st;
@@ -2404,9 +2485,12 @@ int json_decode(kwok_engine* e, const kwok_codec* c, const char* arena, size_t a
         J.cfg_h->all_host = 1;
     }
     HIPCHK(e, hipMemcpyAsync(J.cfg, J.cfg_h, sizeof(JsonCfg), hipMemcpyHostToDevice, st));
-    HIPCHK(e, hipMemcpyAsync(J.off, doc_off, n * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(e, hipMemcpyAsync(J.len, doc_len, n * 4, hipMemcpyHostToDevice, st));
-    if (op) {
+    if (!dev_inputs) {
+        HIPCHK(e, hipMemcpyAsync(J.off, doc_off, n * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipMemcpyAsync(J.len, doc_len, n * 4, hipMemcpyHostToDevice, st));
+    }
+    const bool ingest = op || dev_inputs;
+    if (op && !dev_inputs) {
         HIPCHK(e, hipMemcpyAsync(J.op, op, n, hipMemcpyHostToDevice, st));
         HIPCHK(e, hipMemcpyAsync(J.handle, handle, n * 4, hipMemcpyHostToDevice, st));
     }
@@ -2417,7 +2501,7 @@ int json_decode(kwok_engine* e, const kwok_codec* c, const char* arena, size_t a
     // under the copy, which bounds the call (the link: ~2.7 GB per C4 tick).
     // Otherwise one copy, then one decode.
     bool sorted = true;
-    for (size_t i = 1; i < n && sorted; i++) sorted = doc_off[i] >= doc_off[i - 1] + doc_len[i - 1];
+    for (size_t i = 1; i < n && sorted && !dev_inputs; i++) sorted = doc_off[i] >= doc_off[i - 1] + doc_len[i - 1];
     const uint32_t K = !resident && sorted && arena_len > (64u << 20) ? (uint32_t)std::min<size_t>(8, n / 4096 + 1) : 1u;
     hipStream_t ps = G.pst;
     HIPCHK(e, hipEventRecord(G.go, st));  // the copies start after the engine stream's earlier work
@@ -2443,8 +2527,8 @@ int json_decode(kwok_engine* e, const kwok_codec* c, const char* arena, size_t a
         A.base = (uint32_t)d0;
         A.tab_mask = J.tab_mask;
         A.cfg = J.cfg;
-        A.op = op ? J.op + d0 : nullptr;
-        A.handle = op ? J.handle + d0 : nullptr;
+        A.op = ingest ? J.op + d0 : nullptr;
+        A.handle = ingest ? J.handle + d0 : nullptr;
         A.tab_key = J.tab_key;
         A.tab_id = J.tab_id;
         A.tab_canon = J.tab_canon;
@@ -3473,6 +3557,357 @@ int kwok_resync_stats(kwok_engine* e, uint64_t out[KWOK_RESYNC_STAT_COUNT]) {
         if (int rc = resync_read_counters(e)) return rc;
     for (int k = 0; k < KWOK_RESYNC_STAT_COUNT; k++) out[k] = R.stats[k];
     out[KWOK_RESYNC_STAT_MARKED] = R.ctr_h ? (uint64_t)R.ctr_h->marked : 0;
+    return KWOK_OK;
+}
+
+// ---- the pod uid directory (kwok_watch.h, uid.hip) ---------------------------------
+namespace {
+int uid_read_counters(kwok_engine* e) {
+    auto& U = e->uid;
+    HIPCHK(e, hipMemcpyAsync(U.ctr_h, U.ctr, sizeof(UidCounters), hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    if (U.ctr_h->err) {
+        e->poisoned = true;
+        return e->fail(KWOK_EDEVICE, "uid directory: a probe wrapped the whole table");
+    }
+    return KWOK_OK;
+}
+// the table cleared and every live slot with a uid inserted again (k_uid_rebuild)
+int uid_rebuild(kwok_engine* e) {
+    auto& U = e->uid;
+    hipStream_t st = e->st;
+    HIPCHK(e, hipMemsetAsync(U.tab, 0, U.tab_cap * 8, st));
+    HIPCHK(e, hipMemsetAsync(&U.ctr->entries, 0, sizeof(U.ctr->entries), st));
+    launch_uid_rebuild(e->S, U.dir(), st);
+    HIPCHK(e, hipGetLastError());
+    if (int rc = uid_read_counters(e)) return rc;
+    U.live = U.ctr_h->entries;
+    U.inserted = 0;
+    U.stats[KWOK_UID_STAT_REBUILDS]++;
+    return KWOK_OK;
+}
+// before a launch that may insert `incoming` entries: the table sized for the pod slots (a growth
+// outgrew it), stale entries dropped once live + inserted exceeds half of it
+int uid_ensure(kwok_engine* e, size_t incoming) {
+    auto& U = e->uid;
+    auto want_cap = [&](uint64_t entries) {
+        if (U.forced_log2) return (size_t)1 << U.forced_log2;
+        size_t c = std::max<size_t>(U.tab_cap, 64);
+        while (c < 2 * (uint64_t)e->PL || c < 2 * entries) c <<= 1;
+        return c;
+    };
+    auto resize = [&](size_t cap) -> int {
+        dfree(U.tab);
+        U.tab_cap = 0;
+        if (int rc = dalloc(e, &U.tab, cap)) return rc;
+        U.tab_cap = cap;
+        return uid_rebuild(e);
+    };
+    int rc = 0;
+    if (want_cap(0) != U.tab_cap) {
+        if ((rc = resize(want_cap(0)))) return rc;
+    } else if (U.live + U.inserted + incoming > U.tab_cap / 2 && U.inserted) {
+        if ((rc = uid_rebuild(e))) return rc;
+    }
+    if (U.live + incoming > U.tab_cap / 2) {
+        if (!U.forced_log2) {
+            if ((rc = resize(want_cap(U.live + incoming)))) return rc;
+        } else if (U.live + incoming >= U.tab_cap) {  // (a forced table: filled past half, never to the last entry)
+            return e->fail(KWOK_EFULL, "uid directory: %llu entries and %zu more in a table forced to %zu",
+                           (unsigned long long)U.live, incoming, U.tab_cap);
+        }
+    }
+    U.inserted += incoming;
+    return KWOK_OK;
+}
+// kwok_uid_bind / kwok_uid_lookup: the spans and the caller's arena on the device
+int uid_upload(kwok_engine* e, const int32_t* handles, const char* arena, const uint64_t* off, const uint32_t* len, size_t n,
+               uint64_t* arena_len) {
+    auto& U = e->uid;
+    uint64_t al = 0;
+    for (size_t i = 0; i < n; i++)  // (the bytes the spans name; a span past 2^40 is the caller's error)
+        if (len[i] && len[i] <= KWOK_UID_MAX && off[i] < (1ull << 40)) al = std::max<uint64_t>(al, off[i] + len[i]);
+    int rc = 0;
+    if (n > U.qcap) {
+        dfree(U.q_h), dfree(U.q_off), dfree(U.q_len);
+        U.qcap = 0;
+        const size_t cap = std::max<size_t>(n + n / 4, 4096);
+        if ((rc = dalloc(e, &U.q_h, cap)) || (rc = dalloc(e, &U.q_off, cap)) || (rc = dalloc(e, &U.q_len, cap))) return rc;
+        U.qcap = cap;
+    }
+    if (al + 1 > U.acap) {
+        dfree(U.q_arena);
+        U.acap = 0;
+        const size_t cap = std::max<size_t>(al + al / 4 + 1, 1 << 16);
+        if ((rc = dalloc(e, &U.q_arena, cap))) return rc;
+        U.acap = cap;
+    }
+    hipStream_t st = e->st;
+    if (handles) HIPCHK(e, hipMemcpyAsync(U.q_h, handles, n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(U.q_off, off, n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(U.q_len, len, n * 4, hipMemcpyHostToDevice, st));
+    if (al) HIPCHK(e, hipMemcpyAsync(U.q_arena, arena, al, hipMemcpyHostToDevice, st));
+    *arena_len = al;
+    return KWOK_OK;
+}
+struct NoteSrc {  // the ingest notes the by-uid batch's creates with their uids
+    kwok_engine* e;
+    NoteSrc(kwok_engine* e_, const UidNote* n) : e(e_) { e->uid.note = n; }
+    ~NoteSrc() { e->uid.note = nullptr; }
+};
+}  // namespace
+
+int kwok_uid_dir_enable(kwok_engine* e) {
+    if (!e) return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    if (e->multi) return e->fail(KWOK_EINVAL, "kwok_uid_dir_enable: single-rank engines only");
+    auto& U = e->uid;
+    if (U.on) return KWOK_OK;
+    drain(e);
+    if (e->poisoned) return poisoned(e);
+    if (const char* v = getenv("KWOK_UID_TAB_LOG2")) {
+        const int l = atoi(v);
+        if (l < 4 || l > 31) return e->fail(KWOK_EINVAL, "KWOK_UID_TAB_LOG2 must be 4..31");
+        U.forced_log2 = l;
+    }
+    int rc = 0;  // (dalloc zeroes: no uid known, an empty table)
+    if (!U.ctr) {
+        if ((rc = dalloc(e, &U.ctr, 1)) || (rc = dalloc(e, &U.run, 1))) return rc;
+        if (hipHostMalloc((void**)&U.ctr_h, sizeof(UidCounters), hipHostMallocDefault) != hipSuccess ||
+            hipHostMalloc((void**)&U.run_h, sizeof(UidRun), hipHostMallocDefault) != hipSuccess)
+            return e->fail(KWOK_ENOMEM, "uid directory staging");
+        memset(U.ctr_h, 0, sizeof(UidCounters));
+    }
+    if (!U.pod_uid && (rc = dalloc(e, &U.pod_uid, e->PLa))) return rc;
+    if (!U.pod_uid_len && (rc = dalloc(e, &U.pod_uid_len, e->PLa))) return rc;
+    if (!U.tab) {
+        size_t cap = 64;
+        if (U.forced_log2) cap = (size_t)1 << U.forced_log2;
+        else
+            while (cap < 2 * (uint64_t)e->PL) cap <<= 1;
+        if ((rc = dalloc(e, &U.tab, cap))) return rc;
+        U.tab_cap = cap;
+    }
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    U.on = true;
+    return KWOK_OK;
+}
+
+int kwok_uid_bind(kwok_engine* e, const int32_t* handles, const char* arena, const uint64_t* off, const uint32_t* len,
+                  size_t n, size_t* n_bad) {
+    if (n_bad) *n_bad = 0;
+    if (!e || (n && (!handles || !off || !len)) || n > 0x7FFFFFF0ull) return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    auto& U = e->uid;
+    if (!U.on) return e->fail(KWOK_EINVAL, "kwok_uid_bind: the uid directory is not enabled");
+    drain(e);  // (a handle is judged against the state after every submitted tick)
+    if (e->poisoned) return poisoned(e);
+    if (!n) return KWOK_OK;
+    for (size_t i = 0; i < n; i++)
+        if (len[i] && len[i] <= KWOK_UID_MAX && !arena) return KWOK_EINVAL;
+    int rc = uid_ensure(e, n);
+    if (rc) return rc;
+    uint64_t al = 0;
+    if ((rc = uid_upload(e, handles, arena, off, len, n, &al))) return rc;
+    hipStream_t st = e->st;
+    HIPCHK(e, hipMemsetAsync(&U.ctr->bad, 0, sizeof(U.ctr->bad), st));
+    launch_uid_bind(e->S, U.dir(), U.q_h, U.q_arena, al, U.q_off, U.q_len, (uint32_t)n, st);
+    HIPCHK(e, hipGetLastError());
+    if ((rc = uid_read_counters(e))) return rc;
+    if (n_bad) *n_bad = (size_t)U.ctr_h->bad;
+    return KWOK_OK;
+}
+
+int kwok_uid_lookup(kwok_engine* e, const char* arena, const uint64_t* off, const uint32_t* len, size_t n,
+                    int32_t* out_handles) {
+    if (!e || (n && (!off || !len || !out_handles)) || n > 0x7FFFFFF0ull) return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    auto& U = e->uid;
+    if (!U.on) return e->fail(KWOK_EINVAL, "kwok_uid_lookup: the uid directory is not enabled");
+    drain(e);
+    if (e->poisoned) return poisoned(e);
+    if (!n) return KWOK_OK;
+    for (size_t i = 0; i < n; i++)
+        if (len[i] && len[i] <= KWOK_UID_MAX && !arena) return KWOK_EINVAL;
+    int rc = uid_ensure(e, 0);
+    if (rc) return rc;
+    uint64_t al = 0;
+    if ((rc = uid_upload(e, nullptr, arena, off, len, n, &al))) return rc;
+    hipStream_t st = e->st;
+    launch_uid_lookup(e->S, U.dir(), U.q_arena, al, U.q_off, U.q_len, (uint32_t)n, U.q_h, st);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(out_handles, U.q_h, n * 4, hipMemcpyDeviceToHost, st));
+    return uid_read_counters(e);
+}
+
+int kwok_ingest_pods_framed_uid(kwok_engine* e, const kwok_codec* c, uint64_t stream_id, const uint32_t* frame_idx,
+                                size_t n, int32_t* out_handles, int32_t* out_status, uint32_t* out_released,
+                                size_t* n_host, size_t* n_runs) {
+    if (n_host) *n_host = 0;
+    if (n_runs) *n_runs = 0;
+    if (!e || !c || (n && !frame_idx) || n > 0x7FFFFFF0ull) return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    drain(e);
+    if (e->poisoned) return poisoned(e);
+    auto& U = e->uid;
+    auto& Wt = e->watch;
+    auto& J = e->json;
+    auto& G = e->ing;
+    if (!U.on) return e->fail(KWOK_EINVAL, "kwok_ingest_pods_framed_uid: the uid directory is not enabled");
+    if (!stream_id || stream_id != Wt.id) return e->fail(KWOK_EINVAL, "stream_id is not the resident watch stream");
+    if (!n) return 0;
+    hipStream_t st = e->st;
+    const auto t0 = clk::now();
+    int rc = 0;
+    // the per-record buffers of the call, the decode's and the ingest's sized for the whole batch
+    // (a run is a prefix of a range: no later reserve moves them)
+    if (n > U.cap) {
+        dfree(U.fidx), dfree(U.uoff), dfree(U.res_rel), dfree(U.ulen), dfree(U.cls), dfree(U.hash), dfree(U.res_h), dfree(U.res_st);
+        U.cap = 0;
+        const size_t cap = std::max<size_t>(n + n / 4, 4096);
+        if ((rc = dalloc(e, &U.fidx, cap)) || (rc = dalloc(e, &U.uoff, cap)) || (rc = dalloc(e, &U.res_rel, cap)) ||
+            (rc = dalloc(e, &U.ulen, cap)) || (rc = dalloc(e, &U.cls, cap)) || (rc = dalloc(e, &U.hash, cap)) ||
+            (rc = dalloc(e, &U.res_h, cap)) || (rc = dalloc(e, &U.res_st, cap)))
+            return rc;
+        U.cap = cap;
+    }
+    size_t ccap = 64;
+    while (ccap < 2 * n) ccap <<= 1;
+    if (ccap > U.claim_cap) {
+        dfree(U.claim);
+        U.claim_cap = 0;
+        if ((rc = dalloc(e, &U.claim, ccap))) return rc;
+        U.claim_cap = ccap;
+    }
+    if ((rc = ingest_reserve(e, n, 0)) || (rc = json_reserve(e, n))) return rc;
+    HIPCHK(e, hipMemcpyAsync(U.fidx, frame_idx, n * 4, hipMemcpyHostToDevice, st));
+    // KWOK_INGEST_PROF: device-side stamps around k_uid_resolve and around k_uid_claim + k_uid_cut
+    hipEvent_t pev[3] = {};
+    if (e->iprof)
+        for (auto& x : pev) (void)hipEventCreate(&x);
+    struct PevGuard {
+        hipEvent_t* p;
+        ~PevGuard() {
+            for (int k = 0; k < 3; k++)
+                if (p[k]) (void)hipEventDestroy(p[k]);
+        }
+    } pev_guard{pev};
+    float ms_resolve = 0, ms_cut = 0, ms_note = 0;
+    UidBatch B{};
+    B.stream = Wt.stream;
+    B.stream_len = Wt.len;
+    B.frames = Wt.frames;
+    B.n_frames = (uint32_t)Wt.frames_h.size();
+    B.n = (uint32_t)n;
+    B.frame_idx = U.fidx;
+    B.uoff = U.uoff, B.ulen = U.ulen, B.hash = U.hash, B.cls = U.cls;
+    B.doc_off = J.off, B.doc_len = J.len, B.op = J.op, B.handle = J.handle;
+    B.claim = U.claim;
+    B.run = U.run;
+    B.err = &U.ctr->err;
+    size_t runs = 0, cuts = 0, host_docs = 0;
+    for (size_t lo = 0; lo < n;) {
+        const size_t range = n - lo;
+        if ((rc = uid_ensure(e, 0))) return rc;  // (the table sized for the slots before it is probed)
+        size_t cm = 64;
+        while (cm < 2 * range) cm <<= 1;
+        B.lo = (uint32_t)lo;
+        B.claim_mask = (uint32_t)(cm - 1);
+        U.run_h->first_cut = ~0u, U.run_h->n_sent = 0, U.run_h->n_new = 0, U.run_h->pad = 0;
+        HIPCHK(e, hipMemcpyAsync(U.run, U.run_h, sizeof(UidRun), hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipMemsetAsync(U.claim, 0xFF, cm * 4, st));
+        if (pev[0]) (void)hipEventRecord(pev[0], st);
+        launch_uid_resolve(e->S, U.dir(), B, st);
+        if (pev[1]) (void)hipEventRecord(pev[1], st);
+        launch_uid_cut(B, st);
+        if (pev[2]) (void)hipEventRecord(pev[2], st);
+        HIPCHK(e, hipGetLastError());
+        HIPCHK(e, hipMemcpyAsync(U.run_h, U.run, sizeof(UidRun), hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipStreamSynchronize(st));
+        if (pev[0]) {
+            float a = 0, b = 0;
+            (void)hipEventElapsedTime(&a, pev[0], pev[1]);
+            (void)hipEventElapsedTime(&b, pev[1], pev[2]);
+            ms_resolve += a, ms_cut += b;
+        }
+        const size_t cut = std::min<size_t>(U.run_h->first_cut, n);
+        if (cut <= lo) return e->fail(KWOK_EDEVICE, "uid directory: a run of no records at %zu", lo);
+        const size_t m = cut - lo;
+        // (a cut run holds the create that caused the cut; an uncut one is the whole range, whose count this is)
+        const bool sends = cut < n || U.run_h->n_sent;
+        if (cut < n) cuts++;
+        const int32_t *rh = nullptr, *rs = nullptr;
+        const uint32_t* rr = nullptr;
+        if (sends) {
+            runs++;
+            Wt.stats[KWOK_WATCH_STAT_INGESTS]++;
+            // (room for the run's creates: the range's count, which bounds a cut run's)
+            if ((rc = uid_ensure(e, std::min<size_t>(m, U.run_h->n_new)))) return rc;
+            uint32_t nh = 0;
+            if ((rc = json_decode(e, c, Wt.host, Wt.len, nullptr, nullptr, m, nullptr, nullptr, &nh, Wt.stream, true))) return rc;
+            if (nh) {  // the documents the scanner listed for the host codec: their spans, ops and the run's handles
+                std::vector<uint64_t> off;
+                std::vector<uint32_t> len;
+                std::vector<uint8_t> op;
+                std::vector<int32_t> hv(m);
+                if ((rc = framed_records(e, stream_id, frame_idx + lo, m, off, len, op))) return rc;
+                HIPCHK(e, hipMemcpyAsync(hv.data(), J.handle, m * 4, hipMemcpyDeviceToHost, st));
+                HIPCHK(e, hipStreamSynchronize(st));
+                if ((rc = json_complete(e, c, Wt.host, Wt.len, off.data(), len.data(), nh, op.data(), hv.data(), nullptr, nullptr)))
+                    return rc;
+                host_docs += nh;
+            }
+            const UidNote N{Wt.stream, U.uoff + lo, U.ulen + lo, U.hash + lo, U.cls + lo};
+            NoteSrc note(e, &N);
+            ArenaSrc src(e, Wt.stream);
+            rc = ingest_pods_impl(e, G.d_ev, 0, m, nullptr, Wt.len, nullptr, nullptr, nullptr, nullptr, true);
+            for (size_t q = 0; q + 1 < U.note_ev.size(); q += 2) {  // (the batch is synchronised, or failed)
+                float ms = 0;
+                if (rc >= 0 && hipEventElapsedTime(&ms, U.note_ev[q], U.note_ev[q + 1]) == hipSuccess) ms_note += ms;
+                (void)hipEventDestroy(U.note_ev[q]);
+                (void)hipEventDestroy(U.note_ev[q + 1]);
+            }
+            U.note_ev.clear();
+            if (rc < 0) return rc;
+            rh = G.out_handle, rs = G.out_status, rr = G.out_released;
+        }
+        // (a run that sends nothing holds withheld records only: k_uid_fix reads no result of the ingest for them)
+        launch_uid_fix(B, (uint32_t)m, rh ? rh : U.res_h, rs ? rs : U.res_st, rr ? rr : U.res_rel, U.res_h, U.res_st, U.res_rel, st);
+        HIPCHK(e, hipGetLastError());
+        lo = cut;
+    }
+    if (out_handles) HIPCHK(e, hipMemcpyAsync(out_handles, U.res_h, n * 4, hipMemcpyDeviceToHost, st));
+    if (out_released) HIPCHK(e, hipMemcpyAsync(out_released, U.res_rel, n * 4, hipMemcpyDeviceToHost, st));
+    std::vector<int32_t> st_tmp(out_status ? 0 : n);
+    int32_t* sts = out_status ? out_status : st_tmp.data();
+    HIPCHK(e, hipMemcpyAsync(sts, U.res_st, n * 4, hipMemcpyDeviceToHost, st));
+    if ((rc = uid_read_counters(e))) return rc;
+    int rejected = 0;
+    for (size_t i = 0; i < n; i++) rejected += sts[i] != KWOK_OK && sts[i] != KWOK_NOT_SENT;
+    U.stats[KWOK_UID_STAT_RUNS] += runs;
+    U.stats[KWOK_UID_STAT_CUTS] += cuts;
+    if (n_host) *n_host = host_docs;
+    if (n_runs) *n_runs = runs;
+    if (e->iprof)
+        fprintf(stderr, "[kwok uid] %zu frames, %zu run%s (%zu by the host): k_uid_resolve %.3f ms, k_uid_claim + k_uid_cut %.3f ms, "
+                        "k_uid_note %.3f ms; the call %.2f ms\n", n, runs, runs == 1 ? "" : "s", host_docs, ms_resolve, ms_cut,
+                ms_note, ms_between(t0, clk::now()));
+    return rejected;
+}
+
+int kwok_uid_stats(kwok_engine* e, uint64_t out[KWOK_UID_STAT_COUNT]) {
+    if (!e || !out) return KWOK_EINVAL;
+    auto& U = e->uid;
+    if (U.ctr && !e->poisoned)
+        if (int rc = uid_read_counters(e)) return rc;
+    for (int k = 0; k < KWOK_UID_STAT_COUNT; k++) out[k] = U.stats[k];
+    if (U.ctr_h) {
+        out[KWOK_UID_STAT_LOOKUPS] = U.ctr_h->lookups;
+        out[KWOK_UID_STAT_HITS] = U.ctr_h->hits;
+        out[KWOK_UID_STAT_BINDS] = U.ctr_h->binds;
+        out[KWOK_UID_STAT_UNBOUND] = U.ctr_h->unbound;
+        out[KWOK_UID_STAT_TABLE_ENTRIES] = U.ctr_h->entries;
+    }
     return KWOK_OK;
 }
 

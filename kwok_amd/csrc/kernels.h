@@ -404,4 +404,55 @@ void launch_sweep_count(const DevState& S, int pods, const uint8_t* seen, uint32
 void launch_sweep_emit(const DevState& S, int pods, const uint8_t* seen, const uint32_t* tile_base, uint32_t n_out, void* recs,
                        int32_t* handles, int32_t* nodes, hipStream_t st);
 
+// ---- the pod uid directory (uid.hip, kwok_watch.h): metadata.uid -> pod handle on the device ----
+// (kept out of DevState: no kernel outside uid.hip sees it)
+struct UidDir {
+    uint8_t* pod_uid;         // [PLa][KWOK_UID_MAX] re-laid out with the pod arrays (grow_pods)
+    uint8_t* pod_uid_len;     // [PLa] 0: no uid known
+    unsigned long long* tab;  // [mask + 1] (tag << 32) | (handle + 1), 0: empty
+    uint32_t mask;
+    UidCounters* ctr;
+};
+// a by-uid framed batch: records [lo, n) are the current range (a run is its prefix up to the cut)
+struct UidBatch {
+    const uint8_t* stream;    // the resident stream
+    uint64_t stream_len;
+    const kwok_watch_frame* frames;
+    uint32_t n_frames;
+    uint32_t lo, n;
+    const uint32_t* frame_idx;  // [n]
+    uint32_t* uoff;           // [n] the record's uid span (keyable uids only)
+    uint8_t* ulen;            // [n]
+    uint64_t* hash;           // [n] FNV-1a-64 of the uid
+    uint8_t* cls;             // [n] UID_*
+    uint64_t* doc_off;        // [n - lo] the decode's inputs, run-local
+    uint32_t* doc_len;
+    uint8_t* op;
+    int32_t* handle;
+    uint32_t* claim;          // [claim_mask + 1] >= 2 x (n - lo), record indices, ~0: empty (cleared per run)
+    uint32_t claim_mask;
+    UidRun* run;              // (reset per run)
+    uint32_t* err;            // a probe wrapped the whole table
+};
+// what k_uid_note needs of a by-uid batch, at the chunk's first record (cls null: the entry carries no uid)
+struct UidNote {
+    const uint8_t* stream;
+    const uint32_t* uoff;
+    const uint8_t* ulen;
+    const uint64_t* hash;
+    const uint8_t* cls;
+};
+void launch_uid_resolve(const DevState& S, const UidDir& D, const UidBatch& B, hipStream_t st);
+void launch_uid_cut(const UidBatch& B, hipStream_t st);  // k_uid_claim, k_uid_cut
+// behind the apply pass of a pod chunk (spec: as the pass, nothing when the chunk returned for growth)
+void launch_uid_note(const DevState& S, const IngestBatch& I, const UidDir& D, const UidNote& N, hipStream_t st);
+// records [lo, lo + m): the run's results (run-local h / status / rel) into the call's (out_*), withheld records answered
+void launch_uid_fix(const UidBatch& B, uint32_t m, const int32_t* h, const int32_t* status, const uint32_t* rel, int32_t* out_h,
+                    int32_t* out_status, uint32_t* out_rel, hipStream_t st);
+void launch_uid_bind(const DevState& S, const UidDir& D, const int32_t* handles, const uint8_t* arena, uint64_t arena_len,
+                     const uint64_t* off, const uint32_t* len, uint32_t n, hipStream_t st);
+void launch_uid_lookup(const DevState& S, const UidDir& D, const uint8_t* arena, uint64_t arena_len, const uint64_t* off,
+                       const uint32_t* len, uint32_t n, int32_t* out, hipStream_t st);
+void launch_uid_rebuild(const DevState& S, const UidDir& D, hipStream_t st);
+
 }  // namespace kwok

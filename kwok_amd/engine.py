@@ -125,6 +125,11 @@ def declare(lib, pre):
             "resync_sweep": (C.c_int, [VP, C.c_int, VP, SZ, P(SZ), VP, VP]),
             "resync_end": (C.c_int, [VP, C.c_int]),
             "resync_stats": (C.c_int, [VP, VP]),
+            "uid_dir_enable": (C.c_int, [VP]),
+            "uid_bind": (C.c_int, [VP, VP, VP, VP, VP, SZ, P(SZ)]),
+            "uid_lookup": (C.c_int, [VP, VP, VP, VP, SZ, VP]),
+            "ingest_pods_framed_uid": (C.c_int, [VP, VP, U64, VP, SZ, VP, VP, VP, P(SZ), P(SZ)]),
+            "uid_stats": (C.c_int, [VP, VP]),
         })
     for name, (res, args) in sig.items():
         f = getattr(lib, pre + name, None)
@@ -706,6 +711,59 @@ class Engine(EngineBase):
         out = (C.c_uint64 * len(abi.RESYNC_STATS))()
         self._check(self._lib.kwok_resync_stats(self._h, out), "resync_stats")
         return dict(zip(abi.RESYNC_STATS, list(out)))
+
+    # ---- the pod uid directory (include/kwok_watch.h): metadata.uid -> handle on the device ----
+    @staticmethod
+    def _uid_spans(uids):
+        """uids (bytes or str each) -> (arena, offsets, lengths)"""
+        bs = [u.encode() if isinstance(u, str) else bytes(u) for u in uids]
+        lens = np.fromiter((len(b) for b in bs), np.uint32, len(bs))
+        offs = np.zeros(len(bs), np.uint64)
+        if len(bs) > 1:
+            np.cumsum(lens[:-1], out=offs[1:])
+        arena = np.frombuffer(b"".join(bs) + b"\0", np.uint8)
+        return arena, offs, lens
+
+    def uid_dir_enable(self):
+        """kwok_uid_dir_enable: allocate the directory (idempotent; single-rank engines only)"""
+        self._check(self._lib.kwok_uid_dir_enable(self._h), "uid_dir_enable")
+
+    def uid_bind(self, handles, uids):
+        """kwok_uid_bind: uids[i] becomes the uid of live pod handles[i] -> the records that bound nothing"""
+        hs = np.ascontiguousarray(handles, np.int32)
+        arena, offs, lens = self._uid_spans(uids)
+        assert len(hs) == len(lens)
+        bad = C.c_size_t()
+        rc = self._lib.kwok_uid_bind(self._h, hs.ctypes.data, arena.ctypes.data, offs.ctypes.data, lens.ctypes.data, len(hs),
+                                     C.byref(bad))
+        self._check(rc, "uid_bind")
+        return bad.value
+
+    def uid_lookup(self, uids):
+        """kwok_uid_lookup: the handle of the live pod bound to each uid, or -1"""
+        arena, offs, lens = self._uid_spans(uids)
+        out = np.empty(len(lens), np.int32)
+        rc = self._lib.kwok_uid_lookup(self._h, arena.ctypes.data, offs.ctypes.data, lens.ctypes.data, len(lens),
+                                       out.ctypes.data)
+        self._check(rc, "uid_lookup")
+        return out
+
+    def ingest_pods_framed_uid(self, codec, stream_id, frame_idx):
+        """kwok_ingest_pods_framed_uid: (handles, statuses, released, documents the host decided, runs)"""
+        idx = np.ascontiguousarray(frame_idx, np.uint32)
+        n = len(idx)
+        hs, st, rel = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.uint32)
+        nh, nr = C.c_size_t(), C.c_size_t()
+        rc = self._lib.kwok_ingest_pods_framed_uid(self._h, codec._h, stream_id, idx.ctypes.data, n, hs.ctypes.data,
+                                                   st.ctypes.data, rel.ctypes.data, C.byref(nh), C.byref(nr))
+        self._check(rc, "ingest_pods_framed_uid")
+        return hs, st, rel, nh.value, nr.value
+
+    def uid_stats(self):
+        """kwok_uid_stats: lookups / hits / binds / creates without a uid / runs / cuts / rebuilds / table entries"""
+        out = (C.c_uint64 * len(abi.UID_STATS))()
+        self._check(self._lib.kwok_uid_stats(self._h, out), "uid_stats")
+        return dict(zip(abi.UID_STATS, list(out)))
 
     @staticmethod
     def _arena_arg(arena):
