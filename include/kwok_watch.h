@@ -295,6 +295,76 @@ enum {
 };
 int kwok_uid_stats(kwok_engine* e, uint64_t out[KWOK_UID_STAT_COUNT]);
 
+/* ---- Echo ledger ------------------------------------------------
+ *
+ * The engine's own patches come back on the watch; a controller drops those echoes
+ * by (uid, resourceVersion).  With the ledger enabled that filter runs on the device:
+ * the framed ingests below take ALL frames of a batch, decide the echoes under the
+ * rule of controller.Echoes as _encode / _ingest_frames apply it, and ingest the rest.
+ *
+ * The ledger maps a uid to an ordered list of at most KWOK_ECHO_KEEP resourceVersions
+ * (opaque bytes, compared byte for byte):
+ *   - note(uid, rv) appends; an empty uid or rv is ignored; a ninth note drops the
+ *     oldest; one rv noted twice is held twice;
+ *   - forget(uid) removes every note of the uid;
+ *   - filter, over the records of one call in record order (`seen` empty per call):
+ *       a non-ingestible frame touches neither the ledger nor `seen`;
+ *       DELETED: never an echo; kept, the uid joins `seen` and is forgotten;
+ *       ADDED / MODIFIED: m = the uid's list holds rv; if m its first occurrence is
+ *       removed (dropped or not); the record is dropped iff m and the uid is not in
+ *       `seen`; a record that is not dropped is kept and its uid joins `seen`.
+ * Single-rank engines only. */
+#define KWOK_RV_MAX 24
+#define KWOK_ECHO_KEEP 8
+#define KWOK_ECHO 2 /* per-record status: a frame dropped as the echo of an own patch */
+enum { KWOK_ECHO_NOTE = 0, KWOK_ECHO_FORGET = 1 };
+/* Allocates the ledger (idempotent).  KWOK_EINVAL on a multi-rank engine. */
+int kwok_echo_enable(kwok_engine* e);
+/* op[i] (KWOK_ECHO_NOTE / KWOK_ECHO_FORGET) on uid i = arena[uid_off[i], +uid_len[i]) with
+ * rv i = arena[rv_off[i], +rv_len[i]) (a forget reads no rv), applied in array order per
+ * uid.  out_status[i] (optional): KWOK_OK applied, or an ignored empty uid / rv;
+ * KWOK_EDOMAIN a uid longer than KWOK_UID_MAX or a noted rv longer than KWOK_RV_MAX
+ * (nothing stored); KWOK_EINVAL an unknown op.  A uid need not belong to a live object.
+ * KWOK_EFULL for the call, nothing stored, when a table forced by KWOK_ECHO_TAB_LOG2
+ * cannot take the call's notes.  Returns the number of ops not KWOK_OK, or an error. */
+int kwok_echo_update(kwok_engine* e, const uint8_t* op, const char* arena, const uint64_t* uid_off,
+                     const uint32_t* uid_len, const uint64_t* rv_off, const uint32_t* rv_len, size_t n,
+                     int32_t* out_status);
+/* The filter over typed events: deleted[i] != 0 is a Deleted event.  out_drop[i] = 1: a
+ * dropped echo.  An empty uid or one longer than KWOK_UID_MAX is never an echo; an rv that
+ * is empty or longer than KWOK_RV_MAX matches nothing. */
+int kwok_echo_match(kwok_engine* e, const char* arena, const uint64_t* uid_off, const uint32_t* uid_len,
+                    const uint64_t* rv_off, const uint32_t* rv_len, const uint8_t* deleted, size_t n,
+                    uint8_t* out_drop);
+/* All frames of a batch: the filter first, then the kept records through exactly what
+ * kwok_ingest_pods_framed_uid / kwok_ingest_nodes_framed do with that subset.  A dropped
+ * record: KWOK_ECHO with the handle its uid (pods) or name (nodes) resolves to before the
+ * ingest, or -1.  A frame with KWOK_FRAME_ESC_UID or KWOK_FRAME_ESC_RV: KWOK_EDOMAIN,
+ * handle -1, nothing changes, the ledger untouched.  A non-ingestible frame: KWOK_EINVAL.
+ * An empty uid or one longer than KWOK_UID_MAX is never an echo and follows the
+ * underlying entry.  *n_echoes: the dropped records.  The pod entry needs the uid
+ * directory; both need the ledger (KWOK_EINVAL otherwise).  Returns the number of
+ * records whose status is none of KWOK_OK / KWOK_NOT_SENT / KWOK_ECHO, or an error. */
+int kwok_ingest_pods_framed_echo(kwok_engine* e, const kwok_codec* c, uint64_t stream_id, const uint32_t* frame_idx,
+                                 size_t n, int32_t* out_handles, int32_t* out_status, uint32_t* out_released,
+                                 size_t* n_host, size_t* n_runs, size_t* n_echoes);
+int kwok_ingest_nodes_framed_echo(kwok_engine* e, const kwok_codec* c, uint64_t stream_id, const uint32_t* frame_idx,
+                                  size_t n, int32_t* out_handles, int32_t* out_status, size_t* n_host,
+                                  size_t* n_echoes);
+enum {
+    KWOK_ECHO_STAT_NOTES = 0,     /* notes stored */
+    KWOK_ECHO_STAT_FORGETS,       /* forgets (ops and Deleted records) that removed a note */
+    KWOK_ECHO_STAT_EVICTIONS,     /* ninth notes */
+    KWOK_ECHO_STAT_MATCHED,       /* records whose (uid, rv) was noted */
+    KWOK_ECHO_STAT_DROPPED,       /* ... dropped as echoes */
+    KWOK_ECHO_STAT_KEPT_MATCHED,  /* ... kept: an earlier record of the uid in the call */
+    KWOK_ECHO_STAT_REBUILDS,
+    KWOK_ECHO_STAT_LIVE_UIDS,     /* uids holding a note */
+    KWOK_ECHO_STAT_TABLE_ENTRIES, /* entries of the table, emptied ones included */
+    KWOK_ECHO_STAT_COUNT
+};
+int kwok_echo_stats(kwok_engine* e, uint64_t out[KWOK_ECHO_STAT_COUNT]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -647,6 +647,104 @@ func (g *gpuEngine) ingestPodsFramedUID(codec *gpuCodec, streamID uint64, idx []
 	return handles, status, int(nr), err
 }
 
+// ---- the echo ledger (kwok_watch.h, DESIGN.md §24) ----
+const (
+	echoNote   = uint8(C.KWOK_ECHO_NOTE)
+	echoForget = uint8(C.KWOK_ECHO_FORGET)
+)
+
+// echoEnable: kwok_echo_enable (idempotent; single-rank engines only)
+func (g *gpuEngine) echoEnable() error {
+	if rc := C.kwok_echo_enable(g.h); rc != C.KWOK_OK {
+		return fmt.Errorf("kwok_echo_enable: %d: %s", int(rc), g.lastError())
+	}
+	return nil
+}
+
+// echoSpans: uids then rvs in one arena, with their spans
+func echoSpans(uids, rvs []string) (arena []byte, uo []uint64, ul []uint32, ro []uint64, rl []uint32) {
+	n := len(uids)
+	uo, ul, ro, rl = make([]uint64, n), make([]uint32, n), make([]uint64, n), make([]uint32, n)
+	for i := range uids {
+		uo[i], ul[i] = uint64(len(arena)), uint32(len(uids[i]))
+		arena = append(arena, uids[i]...)
+		ro[i], rl[i] = uint64(len(arena)), uint32(len(rvs[i]))
+		arena = append(arena, rvs[i]...)
+	}
+	return append(arena, 0), uo, ul, ro, rl
+}
+
+// echoUpdate: kwok_echo_update - ops[i] (echoNote / echoForget) on (uids[i], rvs[i]), in order per uid.  A note
+// outside the ledger's domain (KWOK_EDOMAIN) is not stored: its echo is then ingested like any event
+func (g *gpuEngine) echoUpdate(ops []uint8, uids, rvs []string) error {
+	if len(ops) == 0 {
+		return nil
+	}
+	arena, uo, ul, ro, rl := echoSpans(uids, rvs)
+	rc := C.kwok_echo_update(g.h, (*C.uint8_t)(&ops[0]), (*C.char)(unsafe.Pointer(&arena[0])), (*C.uint64_t)(&uo[0]),
+		(*C.uint32_t)(&ul[0]), (*C.uint64_t)(&ro[0]), (*C.uint32_t)(&rl[0]), C.size_t(len(ops)), nil)
+	if rc < 0 {
+		return fmt.Errorf("kwok_echo_update: %d: %s", int(rc), g.lastError())
+	}
+	return nil
+}
+
+// echoMatch: kwok_echo_match - the filter over typed events; drop[i] != 0: the echo of an own patch
+func (g *gpuEngine) echoMatch(uids, rvs []string, deleted []bool) ([]uint8, error) {
+	n := len(uids)
+	drop := make([]uint8, n)
+	if n == 0 {
+		return drop, nil
+	}
+	arena, uo, ul, ro, rl := echoSpans(uids, rvs)
+	del := make([]uint8, n)
+	for i, d := range deleted {
+		if d {
+			del[i] = 1
+		}
+	}
+	rc := C.kwok_echo_match(g.h, (*C.char)(unsafe.Pointer(&arena[0])), (*C.uint64_t)(&uo[0]), (*C.uint32_t)(&ul[0]),
+		(*C.uint64_t)(&ro[0]), (*C.uint32_t)(&rl[0]), (*C.uint8_t)(&del[0]), C.size_t(n), (*C.uint8_t)(&drop[0]))
+	if rc < 0 {
+		return nil, fmt.Errorf("kwok_echo_match: %d: %s", int(rc), g.lastError())
+	}
+	return drop, nil
+}
+
+// ingestPodsFramedEcho: kwok_ingest_pods_framed_echo over ALL frames of a batch - the echoes dropped on the
+// device (status C.KWOK_ECHO, the handle their uid resolves to or -1), the rest as ingestPodsFramedUID
+func (g *gpuEngine) ingestPodsFramedEcho(codec *gpuCodec, streamID uint64, idx []uint32) (handles, status []int32, runs, echoes int, err error) {
+	n := len(idx)
+	handles, status = make([]int32, n), make([]int32, n)
+	if n == 0 {
+		return
+	}
+	released := make([]uint32, n)
+	var nh, nr, ne C.size_t
+	rc := C.kwok_ingest_pods_framed_echo(g.h, codec.c, C.uint64_t(streamID), (*C.uint32_t)(&idx[0]), C.size_t(n),
+		(*C.int32_t)(&handles[0]), (*C.int32_t)(&status[0]), (*C.uint32_t)(&released[0]), &nh, &nr, &ne)
+	if rc < 0 {
+		err = fmt.Errorf("kwok_ingest_pods_framed_echo: %d: %s", int(rc), g.lastError())
+	}
+	return handles, status, int(nr), int(ne), err
+}
+
+// ingestNodesFramedEcho: kwok_ingest_nodes_framed_echo over ALL frames of a batch
+func (g *gpuEngine) ingestNodesFramedEcho(codec *gpuCodec, streamID uint64, idx []uint32) (handles, status []int32, echoes int, err error) {
+	n := len(idx)
+	handles, status = make([]int32, n), make([]int32, n)
+	if n == 0 {
+		return
+	}
+	var nh, ne C.size_t
+	rc := C.kwok_ingest_nodes_framed_echo(g.h, codec.c, C.uint64_t(streamID), (*C.uint32_t)(&idx[0]), C.size_t(n),
+		(*C.int32_t)(&handles[0]), (*C.int32_t)(&status[0]), &nh, &ne)
+	if rc < 0 {
+		err = fmt.Errorf("kwok_ingest_nodes_framed_echo: %d: %s", int(rc), g.lastError())
+	}
+	return handles, status, int(ne), err
+}
+
 // poolPut replicates IPs another rank released at ingest time (multi-GPU).
 func (g *gpuEngine) poolPut(ips []uint32) error {
 	if len(ips) == 0 {

@@ -96,9 +96,19 @@ func (b *objBatch) add(w watchObj) error {
 // a pod's finalizer patch), each with its own echo: every returned version is
 // kept until its echo is seen (the last echoKeep per object, so echoes lost to a
 // watch restart do not pile up).  Any other event of the object is ingested.
+//
+// ledger (KWOK_ECHO_LEDGER=1, with KWOK_UID_DIR=1): the engine's echo ledger (kwok_watch.h, DESIGN.md §24)
+// holds the notes in HBM.  note / forget then only queue their op, in call order; flush sends the queue
+// with one kwok_echo_update; every decision is taken at flush by kwok_echo_match under the same rule
+// (is answers false: nothing is dropped on arrival) and rv stays empty.
 type echoes struct {
 	mu sync.Mutex
 	rv map[types.UID][]string
+
+	ledger *gpuEngine
+	ops    []uint8
+	uids   []string
+	rvs    []string
 }
 
 const echoKeep = 8
@@ -108,6 +118,11 @@ func (x *echoes) note(uid types.UID, rv string) {
 		return
 	}
 	x.mu.Lock()
+	if x.ledger != nil {
+		x.ops, x.uids, x.rvs = append(x.ops, echoNote), append(x.uids, string(uid)), append(x.rvs, rv)
+		x.mu.Unlock()
+		return
+	}
 	v := append(x.rv[uid], rv)
 	if len(v) > echoKeep {
 		v = v[1:]
@@ -121,6 +136,9 @@ func (x *echoes) note(uid types.UID, rv string) {
 func (x *echoes) is(uid types.UID, rv string) bool {
 	x.mu.Lock()
 	defer x.mu.Unlock()
+	if x.ledger != nil { // decided at flush, on the device
+		return false
+	}
 	v := x.rv[uid]
 	for i, r := range v {
 		if r == rv {
@@ -138,8 +156,27 @@ func (x *echoes) is(uid types.UID, rv string) bool {
 
 func (x *echoes) forget(uid types.UID) {
 	x.mu.Lock()
-	delete(x.rv, uid)
+	if x.ledger != nil {
+		if uid != "" {
+			x.ops, x.uids, x.rvs = append(x.ops, echoForget), append(x.uids, string(uid)), append(x.rvs, "")
+		}
+	} else {
+		delete(x.rv, uid)
+	}
 	x.mu.Unlock()
+}
+
+// flush (ledger): the queued notes and forgets in one kwok_echo_update, applied in queue order per uid.
+// Called when every apply of the previous tick has returned, before the batches are filtered
+func (x *echoes) flush() error {
+	x.mu.Lock()
+	ops, uids, rvs := x.ops, x.uids, x.rvs
+	x.ops, x.uids, x.rvs = nil, nil, nil
+	x.mu.Unlock()
+	if x.ledger == nil || len(ops) == 0 {
+		return nil
+	}
+	return x.ledger.echoUpdate(ops, uids, rvs)
 }
 
 // encode drops the echoes among ws (those whose patch returned after the watch
@@ -147,6 +184,26 @@ func (x *echoes) forget(uid types.UID) {
 func (x *echoes) encode(ws []watchObj) (objBatch, int, error) {
 	var b objBatch
 	dropped := 0
+	if x.ledger != nil && len(ws) > 0 { // the same rule, decided by the device ledger (kwok_echo_match)
+		uids, rvs, del := make([]string, len(ws)), make([]string, len(ws)), make([]bool, len(ws))
+		for i, w := range ws {
+			uids[i], rvs[i], del[i] = string(w.uid), w.rv, w.deleted
+		}
+		drop, err := x.ledger.echoMatch(uids, rvs, del)
+		if err != nil {
+			return b, 0, err
+		}
+		for i, w := range ws {
+			if drop[i] != 0 {
+				dropped++
+				continue
+			}
+			if err := b.add(w); err != nil {
+				return b, dropped, err
+			}
+		}
+		return b, dropped, nil
+	}
 	seen := map[types.UID]struct{}{} // (the rule of onEvent: only before any kept event of the object)
 	for _, w := range ws {
 		_, after := seen[w.uid]
@@ -217,13 +274,27 @@ func newGPUController(conf Config, interval time.Duration) (*GPUController, erro
 			return nil, err
 		}
 	}
+	var ledger *gpuEngine
+	if os.Getenv("KWOK_ECHO_LEDGER") == "1" {
+		if !byUID {
+			codec.close()
+			eng.close()
+			return nil, fmt.Errorf("KWOK_ECHO_LEDGER=1 needs KWOK_UID_DIR=1")
+		}
+		if err := eng.echoEnable(); err != nil {
+			codec.close()
+			eng.close()
+			return nil, err
+		}
+		ledger = eng
+	}
 	return &GPUController{
 		byUID: byUID,
 		conf: conf, eng: eng, codec: codec, interval: interval, finalizer: finalizerPatch(),
 		nodeName: map[int32]string{}, nodeHandle: map[string]int32{}, podByUID: map[types.UID]int32{},
 		podUID: map[int32]types.UID{},
 		podRef: map[int32]types.NamespacedName{},
-		echo:     echoes{rv: map[types.UID][]string{}},
+		echo:     echoes{rv: map[types.UID][]string{}, ledger: ledger},
 		queued:   map[types.UID]struct{}{},
 		gpuCodec: os.Getenv("KWOK_GPU_CODEC") != "0",
 	}, nil
@@ -489,7 +560,11 @@ func (c *GPUController) step(ctx context.Context, tasks *parallelTasks, now int6
 	c.nodes, c.pods, c.queued = nil, nil, map[types.UID]struct{}{}
 	c.mu.Unlock()
 	// every apply of the previous tick has returned (loop waits for the task pool):
-	// the echoes that overtook their patch's response are dropped here
+	// the echoes that overtook their patch's response are dropped here (ledger: the previous tick's
+	// notes and forgets go to the device first)
+	if err := c.echo.flush(); err != nil {
+		return 0, err
+	}
 	nb, _, err := c.echo.encode(nw)
 	if err != nil {
 		return 0, err

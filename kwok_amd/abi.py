@@ -122,6 +122,12 @@ RESYNC_STATS = ("sessions", "marked", "swept_nodes", "swept_pods", "released")  
 UID_MAX = 40   # KWOK_UID_MAX: the longest uid the pod uid directory keys
 NOT_SENT = 1   # KWOK_NOT_SENT: a Deleted event of a pod the engine does not hold (controller.NOT_SENT)
 UID_STATS = ("lookups", "hits", "binds", "unbound", "runs", "cuts", "rebuilds", "table_entries")  # KWOK_UID_STAT_* order
+RV_MAX = 24     # KWOK_RV_MAX: the longest resourceVersion the echo ledger notes
+ECHO_KEEP = 8   # KWOK_ECHO_KEEP: the notes the ledger keeps per uid (controller.Echoes.ECHO_KEEP)
+ECHO = 2        # KWOK_ECHO: a frame dropped as the echo of one of the engine's own patches
+ECHO_NOTE, ECHO_FORGET = 0, 1  # kwok_echo_update ops
+ECHO_STATS = ("notes", "forgets", "evictions", "matched", "dropped", "kept_matched", "rebuilds", "live_uids",
+              "table_entries")  # KWOK_ECHO_STAT_* order
 
 
 class ListInfo(C.Structure):

@@ -293,6 +293,7 @@ class Stats:
     resync_swept_pods: int = 0
     resync_skipped: int = 0     # ... sessions closed without a sweep (a bad page, frame or record: a partial picture)
     bodies: int = 0
+    echo_notes_refused: int = 0  # echo_ledger: notes the device ledger refused (a uid / version outside its domain)
     rejected: list = field(default_factory=list)
 
 
@@ -309,12 +310,14 @@ class Controller:
                     max_pod_specs=4096)
 
     def __init__(self, conf: Config, backend=None, codec_threads=1, suppress_echoes=True, geometry=None,
-                 gpu_codec=True, uid_directory=False):
+                 gpu_codec=True, uid_directory=False, echo_ledger=False):
         self.conf = conf
         # uid_directory: the engine's pod uid directory (kwok_watch.h) resolves metadata.uid -> handle on
         # the device; pod_by_uid stays empty (a uid the directory cannot key - empty, escaped in the
         # stream, longer than abi.UID_MAX - is rejected with KWOK_EDOMAIN, where the map would take it)
         self.uid_dir = bool(uid_directory)
+        if echo_ledger and not uid_directory:
+            raise ValueError("echo_ledger needs uid_directory=True")
         self.suppress = suppress_echoes  # False: every echo re-ingested (tests: the A/B that echoes change nothing)
         custom = {}
         if conf.pod_status_template is not None:
@@ -332,6 +335,15 @@ class Controller:
             if not hasattr(self.eng, "uid_dir_enable"):
                 raise ValueError("uid_directory needs the engine backend (kwok_uid_dir_enable)")
             self.eng.uid_dir_enable()
+        # echo_ledger: the engine's echo ledger (kwok_watch.h) holds the notes of the engine's own patches and
+        # drops their echoes on the device: raw frames go to the ingest unfiltered, typed events ask
+        # kwok_echo_match, every decision is taken at flush (echoes_on_arrival stays 0) and self.echo stays empty
+        self.ledger = bool(echo_ledger)
+        self.echo_q = []      # (op, uid, rv) queued for the next kwok_echo_update, in call order
+        if self.ledger:
+            if not hasattr(self.eng, "echo_enable"):
+                raise ValueError("echo_ledger needs the engine backend (kwok_echo_enable)")
+            self.eng.echo_enable()
         self.codec = Codec(manage_all_nodes=conf.manage_all_nodes,
                            manage_nodes_with_annotation_selector=conf.manage_nodes_with_annotation_selector,
                            manage_nodes_with_label_selector=conf.manage_nodes_with_label_selector,
@@ -417,7 +429,8 @@ class Controller:
         # an echo is dropped only while no other event of its object waits in this
         # tick's batch: after one (a change the engine has not seen, older than the
         # engine's patch) the echo is the object's newest state - it carries both
-        if self.suppress and typ == "MODIFIED" and self.echo.is_echo(w.uid, w.rv) and w.uid not in self.queued:
+        if (self.suppress and not self.ledger and typ == "MODIFIED" and self.echo.is_echo(w.uid, w.rv)
+                and w.uid not in self.queued):
             self.stats.echoes_on_arrival += 1
             return
         self.queued.add(w.uid)
@@ -466,7 +479,34 @@ class Controller:
             n += self._tick(now, heartbeats=False)
         return n
 
+    # ---- the notes of the engine's own patches: the host Echoes, or queued for the device ledger ----
+    def _note(self, uid, rv):
+        if self.ledger:
+            if uid and rv:
+                self.echo_q.append((abi.ECHO_NOTE, uid, rv))
+        else:
+            self.echo.note(uid, rv)
+
+    def _forget(self, uid):
+        if self.ledger:
+            if uid:
+                self.echo_q.append((abi.ECHO_FORGET, uid, ""))
+        else:
+            self.echo.forget(uid)
+
+    def _send_echo(self):
+        """the queued notes and forgets in one kwok_echo_update (applied in queue order per uid)"""
+        q, self.echo_q = self.echo_q, []
+        if q:
+            st = self.eng.echo_update([x[0] for x in q], [x[1] for x in q], [x[2] for x in q])
+            self.stats.echo_notes_refused += int((st != abi.OK).sum())  # (a uid / version outside the ledger's domain)
+
     def _encode(self, ws):
+        if self.ledger and self.suppress and ws:  # the same rule, decided by the device ledger
+            drop = self.eng.echo_match([w.uid for w in ws], [w.rv for w in ws], [w.deleted for w in ws])
+            self.stats.echoes_at_flush += int(drop.sum())
+            keep = [w for w, d in zip(ws, drop) if not d]
+            return keep, [json.dumps(w.obj, separators=(",", ":")).encode() for w in keep]
         keep, seen = [], set()
         for w in ws:
             # (the same rule as on arrival: only before any kept event of the object)
@@ -707,8 +747,9 @@ class Controller:
         if nodes:
             for h in hs.tolist():
                 self.node_handle.pop(self.node_name.pop(h, None), None)
-                self.echo.forget(self.node_uid.pop(h, None))
+                self._forget(self.node_uid.pop(h, None))
             self.stats.resync_swept_nodes += len(hs)
+            self._send_echo()
             return
         for h, n in zip(hs.tolist(), nd.tolist()):
             uid = self.pod_uid.get(h)
@@ -720,8 +761,9 @@ class Controller:
             self.pod_uid.pop(h, None)
             self.pod_ref.pop(h, None)
             self.pod_by_uid.pop(uid, None)
-            self.echo.forget(uid)
+            self._forget(uid)
         self.stats.resync_swept_pods += len(hs)
+        self._send_echo()
 
     def _ingest_frames(self, nodes, stream, frames, sid, sess=None):
         """step 1-3 over the frames of the resident stream (a watch stream's lines or
@@ -732,6 +774,8 @@ class Controller:
 
         name = lambda i: text(frames[i], "name", abi.FRAME_ESC_NAME)  # noqa: E731
         ns = lambda i: text(frames[i], "namespace_", abi.FRAME_ESC_NS)  # noqa: E731
+        if self.ledger and self.suppress:
+            return self._ingest_frames_ledger(nodes, stream, frames, sid, sess, text, name, ns)
         keep, uids, deleted, seen, echoed = [], [], [], set(), []
         for i, f in enumerate(frames):
             if f["status"] != abi.OK:
@@ -824,6 +868,97 @@ class Controller:
                 self.pod_uid[h] = uids[k]
                 self.pod_ref[h] = (ns(i), name(i))
 
+    def _ingest_frames_ledger(self, nodes, stream, frames, sid, sess, text, name, ns):
+        """_ingest_frames with the echo ledger: ALL frames of the batch in one call per kind, the echoes
+        dropped on the device; the counters come from the frame array and the statuses, names are decoded
+        only for the records the controller book-keeps (creates, deletes, rejected records)"""
+        n = len(frames)
+        if not n:
+            return
+        kind = abi.KIND_NODES if nodes else abi.KIND_PODS
+        partial = (abi.EDOMAIN, abi.EINVAL, abi.EFULL)
+        ty, fl = frames["type"], frames["flags"]
+        bad = frames["status"] != abi.OK
+        self.stats.watch_bad_frames += int(bad.sum())
+        if sess is not None and bad.any():
+            sess["dirty"] = True
+        self.stats.watch_skipped += int((~bad & np.isin(ty, (abi.WATCH_BOOKMARK, abi.WATCH_ERROR))).sum())
+        ing = ~bad & np.isin(ty, (abi.WATCH_ADDED, abi.WATCH_MODIFIED, abi.WATCH_DELETED))
+        if not ing.any():
+            return
+        uid_of = lambda i: text(frames[i], "uid", abi.FRAME_ESC_UID)  # noqa: E731
+        runs = 0
+        if nodes:
+            hs, st, nh, ne = self.eng.ingest_nodes_framed_echo(self.codec, sid, np.arange(n, dtype=np.uint32))
+        else:
+            hs, st, _rel, nh, runs, ne = self.eng.ingest_pods_framed_echo(self.codec, sid, np.arange(n, dtype=np.uint32))
+        self.stats.echoes_at_flush += ne
+        # a frame whose uid / resourceVersion holds an escape is not decided on the device (no apiserver sends one):
+        # the typed filter on its decoded text, then the plain framed entry - behind the batch's other records
+        esc = np.nonzero(ing & ((fl & (abi.FRAME_ESC_UID | abi.FRAME_ESC_RV)) != 0))[0]
+        if len(esc):
+            drop = self.eng.echo_match([uid_of(i) for i in esc],
+                                       [text(frames[i], "resource_version", abi.FRAME_ESC_RV) for i in esc],
+                                       ty[esc] == abi.WATCH_DELETED)
+            self.stats.echoes_at_flush += int(drop.sum())
+            st[esc[drop != 0]] = abi.ECHO
+            if nodes:  # (an echo's handle: the name the controller knows)
+                for i in esc[drop != 0]:
+                    hs[i] = self.node_handle.get(name(i), -1)
+            late = esc[drop == 0].astype(np.uint32)
+            if len(late):
+                if nodes:
+                    hs[late], st[late], nh2 = self.eng.ingest_nodes_framed(self.codec, sid, late)
+                else:
+                    hs[late], st[late], _rel, nh2, r2 = self.eng.ingest_pods_framed_uid(self.codec, sid, late)
+                    runs += r2
+                nh += nh2
+        if sess is not None:  # seen in the list, not ingested: marked by the handle the device resolved
+            marks = hs[ing & (st == abi.ECHO) & (hs >= 0)]
+            if len(marks):
+                self.eng.resync_mark(kind, marks)
+        keep = np.nonzero(ing & (st != abi.ECHO))[0]
+        if nodes:
+            self.stats.node_docs_host += nh
+            self.stats.node_records += int(np.isin(st[keep], (abi.EDOMAIN, abi.EINVAL), invert=True).sum())
+            for i in keep.tolist():
+                h = int(hs[i])
+                if st[i] != abi.OK:
+                    if st[i] in (abi.EDOMAIN, abi.EINVAL):
+                        self.stats.rejected.append(("node", name(i), int(st[i])))
+                    if sess is not None and st[i] in partial:
+                        sess["dirty"] = True
+                elif ty[i] == abi.WATCH_DELETED:
+                    self.node_name.pop(h, None)
+                    self.node_handle.pop(name(i), None)
+                    self.node_uid.pop(h, None)
+                elif h not in self.node_name:  # a create (a known node keeps its name and uid)
+                    self.node_name[h] = name(i)
+                    self.node_handle[name(i)] = h
+                    self.node_uid[h] = uid_of(i)
+            return
+        self.stats.pod_records += int((st[keep] != NOT_SENT).sum())
+        self.stats.pod_runs += runs
+        self.stats.pod_docs_host += nh
+        for i in keep.tolist():
+            h = int(hs[i])
+            if st[i] not in (abi.OK, NOT_SENT):
+                self.stats.rejected.append(("pod", name(i), int(st[i])))
+                if sess is not None and st[i] in partial:
+                    sess["dirty"] = True
+            elif ty[i] == abi.WATCH_DELETED:
+                if self.conf.enable_cni and self.conf.cni:  # (_ingest_frames: the document is read for spec.nodeName)
+                    f = frames[i]
+                    obj = json.loads(stream[int(f["doc_off"]):int(f["doc_off"]) + int(f["doc_len"])])
+                    if self.has((obj.get("spec") or {}).get("nodeName", "")):
+                        self.conf.cni.remove(uid_of(i), name(i), ns(i))
+                if st[i] == abi.OK:
+                    self.pod_uid.pop(h, None)
+                    self.pod_ref.pop(h, None)
+            elif h not in self.pod_ref:  # a create (a known pod keeps its uid and name)
+                self.pod_uid[h] = uid_of(i)
+                self.pod_ref[h] = (ns(i), name(i))
+
     def _setup_cni(self):
         hs = self.eng.cni_pending()
         if not len(hs):
@@ -873,7 +1008,7 @@ class Controller:
             # the engine freed the handle: the pod's noted echoes go BEFORE the apply, so
             # that the echo of its finalizer patch (noted by the apply) is dropped
             # (gpu_controller.go forgets in the tick callback, ahead of the task)
-            self.echo.forget(self.pod_uid.get(int(h)))
+            self._forget(self.pod_uid.get(int(h)))
             self._apply(DELETE_FIN if f else DELETE, int(h), None)
             gone.append(int(h))
             n += 1
@@ -882,6 +1017,7 @@ class Controller:
             self.pod_by_uid.pop(uid, None)
             self.pod_ref.pop(h, None)
         self.stats.bodies += n
+        self._send_echo()
         return n
 
     def _apply_patches(self, kind, hs, offs, lens):
@@ -905,14 +1041,14 @@ class Controller:
                 obj = cs.patch_node_status(self.node_name[h], body)
             except NotFound:
                 return
-            self.echo.note(_meta(obj).get("uid"), _meta(obj).get("resourceVersion"))
+            self._note(_meta(obj).get("uid"), _meta(obj).get("resourceVersion"))
         elif kind == POD_PATCH:  # LockPod (pod_controller.go:205-231)
             ns, name = self.pod_ref[h]
             try:
                 obj = cs.patch_pod_status(ns, name, body)
             except NotFound:
                 return
-            self.echo.note(_meta(obj).get("uid"), _meta(obj).get("resourceVersion"))
+            self._note(_meta(obj).get("uid"), _meta(obj).get("resourceVersion"))
             if b'"podIP"' not in body:  # an empty status: its echo re-enters (step 6)
                 self.reenter.append(obj)
         else:  # DeletePod (pod_controller.go:155-183)
@@ -925,7 +1061,7 @@ class Controller:
                     obj = cs.patch_pod(ns, name, self.finalizer)
                 except NotFound:
                     return
-                self.echo.note(_meta(obj).get("uid"), _meta(obj).get("resourceVersion"))
+                self._note(_meta(obj).get("uid"), _meta(obj).get("resourceVersion"))
             try:
                 cs.delete_pod(ns, name)
             except NotFound:

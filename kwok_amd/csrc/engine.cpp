@@ -37,6 +37,7 @@
 #include "device.h"
 #include "gotemplate.h"
 #include "kernels.h"
+#include "echo.h"
 #include "templates.h"
 
 using namespace kwok;
@@ -333,6 +334,40 @@ struct kwok_engine {
         uint64_t stats[KWOK_UID_STAT_COUNT] = {};
         UidDir dir() const { return UidDir{reinterpret_cast<uint8_t*>(pod_uid), pod_uid_len, tab, (uint32_t)(tab_cap - 1), ctr}; }
     } uid;
+
+    // ---- the echo ledger (echo.hip, kwok_watch.h): the pool of noted uids behind its table,
+    // the per-call buffers of a filtered batch ----
+    struct Echo {
+        bool on = false;
+        uint32_t* tab = nullptr;
+        size_t tab_cap = 0;           // entries (a power of two)
+        EchoEntry* pool = nullptr;
+        size_t pool_cap = 0;
+        int forced_log2 = 0;          // KWOK_ECHO_TAB_LOG2 (tests)
+        EchoCounters* ctr = nullptr;  // device
+        EchoCounters* ctr_h = nullptr;  // pinned: the counters after the last call
+        EchoCall* call = nullptr;     // device
+        EchoCall* call_h = nullptr;   // pinned
+        uint64_t rebuilds = 0;
+        // per record of a call
+        size_t cap = 0;
+        uint32_t *uoff = nullptr, *roff = nullptr, *own = nullptr, *cnt = nullptr, *fill = nullptr, *lbase = nullptr,
+                 *list = nullptr, *fidx = nullptr, *bsum = nullptr, *kidx = nullptr, *kpos = nullptr, *q_len = nullptr,
+                 *res_rel = nullptr;
+        uint8_t *ulen = nullptr, *rlen = nullptr, *kind = nullptr, *res = nullptr;
+        uint64_t *hash = nullptr, *q_off = nullptr;
+        int32_t *hdrop = nullptr, *res_h = nullptr, *res_st = nullptr;
+        uint32_t* claim = nullptr;
+        size_t claim_cap = 0;
+        // the typed front end: spans, ops, statuses and the caller's arena
+        size_t scap = 0, acap = 0;
+        uint64_t *s_uoff = nullptr, *s_roff = nullptr;
+        uint32_t *s_ulen = nullptr, *s_rlen = nullptr;
+        uint8_t* s_op = nullptr;
+        int32_t* s_status = nullptr;
+        uint8_t* arena = nullptr;
+        EchoLedger ledger() const { return EchoLedger{tab, (uint32_t)(tab_cap - 1), pool, (uint32_t)pool_cap, ctr}; }
+    } echo;
 
     // ---- the pod codec on the GPU (json.hip): per-document buffers, the codec's
     // selectors, the spec table (kwok_spec_key -> spec id) ----
@@ -1288,6 +1323,16 @@ void kwok_engine_destroy(kwok_engine* e) {
             if (p) (void)hipFree(p);
         if (U.ctr_h) (void)hipHostFree(U.ctr_h);
         if (U.run_h) (void)hipHostFree(U.run_h);
+    }
+    {
+        auto& E = e->echo;
+        void* ep[] = {E.tab, E.pool, E.ctr, E.call, E.uoff, E.roff, E.own, E.cnt, E.fill, E.lbase, E.list, E.fidx, E.bsum,
+                      E.kidx, E.kpos, E.q_len, E.res_rel, E.ulen, E.rlen, E.kind, E.res, E.hash, E.q_off, E.hdrop, E.res_h,
+                      E.res_st, E.claim, E.s_uoff, E.s_roff, E.s_ulen, E.s_rlen, E.s_op, E.s_status, E.arena};
+        for (void* p : ep)
+            if (p) (void)hipFree(p);
+        if (E.ctr_h) (void)hipHostFree(E.ctr_h);
+        if (E.call_h) (void)hipHostFree(E.call_h);
     }
     if (e->h_xall) (void)hipHostFree(e->h_xall);
     if (e->pinned) (void)hipHostFree(e->pinned);
@@ -3740,12 +3785,25 @@ int kwok_uid_lookup(kwok_engine* e, const char* arena, const uint64_t* off, cons
     return uid_read_counters(e);
 }
 
+namespace {
+// dev_idx: the frame indices are on the device (the echo entries' kept records; frame_idx null) and the
+// results stay there (uid.res_h / res_st / res_rel): nothing is copied back, 0 is returned
+int pods_framed_uid_impl(kwok_engine* e, const kwok_codec* c, uint64_t stream_id, const uint32_t* frame_idx,
+                         const uint32_t* dev_idx, size_t n, int32_t* out_handles, int32_t* out_status, uint32_t* out_released,
+                         size_t* n_host, size_t* n_runs);
+}
 int kwok_ingest_pods_framed_uid(kwok_engine* e, const kwok_codec* c, uint64_t stream_id, const uint32_t* frame_idx,
                                 size_t n, int32_t* out_handles, int32_t* out_status, uint32_t* out_released,
                                 size_t* n_host, size_t* n_runs) {
     if (n_host) *n_host = 0;
     if (n_runs) *n_runs = 0;
     if (!e || !c || (n && !frame_idx) || n > 0x7FFFFFF0ull) return KWOK_EINVAL;
+    return pods_framed_uid_impl(e, c, stream_id, frame_idx, nullptr, n, out_handles, out_status, out_released, n_host, n_runs);
+}
+namespace {
+int pods_framed_uid_impl(kwok_engine* e, const kwok_codec* c, uint64_t stream_id, const uint32_t* frame_idx,
+                         const uint32_t* dev_idx, size_t n, int32_t* out_handles, int32_t* out_status, uint32_t* out_released,
+                         size_t* n_host, size_t* n_runs) {
     if (e->poisoned) return poisoned(e);
     drain(e);
     if (e->poisoned) return poisoned(e);
@@ -3780,7 +3838,9 @@ int kwok_ingest_pods_framed_uid(kwok_engine* e, const kwok_codec* c, uint64_t st
         U.claim_cap = ccap;
     }
     if ((rc = ingest_reserve(e, n, 0)) || (rc = json_reserve(e, n))) return rc;
-    HIPCHK(e, hipMemcpyAsync(U.fidx, frame_idx, n * 4, hipMemcpyHostToDevice, st));
+    if (dev_idx) HIPCHK(e, hipMemcpyAsync(U.fidx, dev_idx, n * 4, hipMemcpyDeviceToDevice, st));
+    else HIPCHK(e, hipMemcpyAsync(U.fidx, frame_idx, n * 4, hipMemcpyHostToDevice, st));
+    std::vector<uint32_t> idx_h;  // (dev_idx: fetched for the documents the host completes)
     // KWOK_INGEST_PROF: device-side stamps around k_uid_resolve and around k_uid_claim + k_uid_cut
     hipEvent_t pev[3] = {};
     if (e->iprof)
@@ -3850,7 +3910,12 @@ int kwok_ingest_pods_framed_uid(kwok_engine* e, const kwok_codec* c, uint64_t st
                 std::vector<uint32_t> len;
                 std::vector<uint8_t> op;
                 std::vector<int32_t> hv(m);
-                if ((rc = framed_records(e, stream_id, frame_idx + lo, m, off, len, op))) return rc;
+                if (dev_idx && idx_h.empty()) {
+                    idx_h.resize(n);
+                    HIPCHK(e, hipMemcpyAsync(idx_h.data(), U.fidx, n * 4, hipMemcpyDeviceToHost, st));
+                    HIPCHK(e, hipStreamSynchronize(st));
+                }
+                if ((rc = framed_records(e, stream_id, (dev_idx ? idx_h.data() : frame_idx) + lo, m, off, len, op))) return rc;
                 HIPCHK(e, hipMemcpyAsync(hv.data(), J.handle, m * 4, hipMemcpyDeviceToHost, st));
                 HIPCHK(e, hipStreamSynchronize(st));
                 if ((rc = json_complete(e, c, Wt.host, Wt.len, off.data(), len.data(), nh, op.data(), hv.data(), nullptr, nullptr)))
@@ -3876,6 +3941,14 @@ int kwok_ingest_pods_framed_uid(kwok_engine* e, const kwok_codec* c, uint64_t st
         HIPCHK(e, hipGetLastError());
         lo = cut;
     }
+    if (dev_idx) {
+        if ((rc = uid_read_counters(e))) return rc;
+        U.stats[KWOK_UID_STAT_RUNS] += runs;
+        U.stats[KWOK_UID_STAT_CUTS] += cuts;
+        if (n_host) *n_host = host_docs;
+        if (n_runs) *n_runs = runs;
+        return 0;
+    }
     if (out_handles) HIPCHK(e, hipMemcpyAsync(out_handles, U.res_h, n * 4, hipMemcpyDeviceToHost, st));
     if (out_released) HIPCHK(e, hipMemcpyAsync(out_released, U.res_rel, n * 4, hipMemcpyDeviceToHost, st));
     std::vector<int32_t> st_tmp(out_status ? 0 : n);
@@ -3894,6 +3967,7 @@ int kwok_ingest_pods_framed_uid(kwok_engine* e, const kwok_codec* c, uint64_t st
                 ms_note, ms_between(t0, clk::now()));
     return rejected;
 }
+}  // namespace
 
 int kwok_uid_stats(kwok_engine* e, uint64_t out[KWOK_UID_STAT_COUNT]) {
     if (!e || !out) return KWOK_EINVAL;
@@ -3908,6 +3982,391 @@ int kwok_uid_stats(kwok_engine* e, uint64_t out[KWOK_UID_STAT_COUNT]) {
         out[KWOK_UID_STAT_UNBOUND] = U.ctr_h->unbound;
         out[KWOK_UID_STAT_TABLE_ENTRIES] = U.ctr_h->entries;
     }
+    return KWOK_OK;
+}
+
+// ---- the echo ledger (kwok_watch.h, echo.hip) ----------------------------------------
+namespace {
+int echo_read(kwok_engine* e, bool call) {
+    auto& E = e->echo;
+    if (call) HIPCHK(e, hipMemcpyAsync(E.call_h, E.call, sizeof(EchoCall), hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipMemcpyAsync(E.ctr_h, E.ctr, sizeof(EchoCounters), hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    if (E.ctr_h->err || (call && E.call_h->err)) {
+        e->poisoned = true;
+        return e->fail(KWOK_EDEVICE, "echo ledger: a probe wrapped a whole table (ledger %u, call %u)", E.ctr_h->err,
+                       call ? E.call_h->err : 0u);
+    }
+    return KWOK_OK;
+}
+// every entry that holds a note into a fresh pool and table of tab_cap entries (k_echo_rebuild)
+int echo_rebuild(kwok_engine* e, size_t tab_cap) {
+    auto& E = e->echo;
+    hipStream_t st = e->st;
+    const EchoLedger from = E.ledger();
+    const uint32_t used = E.ctr_h->used;
+    uint32_t* tab = nullptr;
+    EchoEntry* pool = nullptr;
+    const size_t pool_cap = E.forced_log2 ? tab_cap - 1 : tab_cap / 2;
+    int rc = 0;
+    if ((rc = dalloc(e, &tab, tab_cap))) return rc;
+    if ((rc = dalloc(e, &pool, pool_cap))) {
+        dfree(tab);
+        return rc;
+    }
+    const EchoLedger to{tab, (uint32_t)(tab_cap - 1), pool, (uint32_t)pool_cap, E.ctr};
+    HIPCHK(e, hipMemsetAsync(&E.ctr->used, 0, sizeof(uint32_t), st));
+    launch_echo_rebuild(from, to, used, st);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipStreamSynchronize(st));
+    dfree(E.tab), dfree(E.pool);
+    E.tab = tab, E.tab_cap = tab_cap, E.pool = pool, E.pool_cap = pool_cap;
+    E.rebuilds++;
+    if ((rc = echo_read(e, false))) return rc;
+    if (E.ctr_h->used != E.ctr_h->live) {
+        e->poisoned = true;
+        return e->fail(KWOK_EDEVICE, "echo ledger: %u entries rebuilt, %llu uids hold a note", E.ctr_h->used,
+                       (unsigned long long)E.ctr_h->live);
+    }
+    return KWOK_OK;
+}
+// before a launch that may insert `incoming` entries: room in the pool, the table at most half full
+// (a forced table: never to its last entry); emptied entries are compacted away first
+int echo_ensure(kwok_engine* e, size_t incoming) {
+    auto& E = e->echo;
+    const uint64_t used = E.ctr_h->used, live = E.ctr_h->live;
+    if (used + incoming <= E.pool_cap) return KWOK_OK;
+    if (E.forced_log2) {
+        if (live + incoming > E.pool_cap)
+            return e->fail(KWOK_EFULL, "echo ledger: %llu uids and %zu more in a table forced to %zu", (unsigned long long)live,
+                           incoming, E.tab_cap);
+        return echo_rebuild(e, E.tab_cap);
+    }
+    size_t cap = 64;
+    while (cap < 2 * (live + incoming)) cap <<= 1;
+    if (cap > ((size_t)1 << 31)) return e->fail(KWOK_EFULL, "echo ledger: %llu uids", (unsigned long long)(live + incoming));
+    return echo_rebuild(e, std::max(cap, E.tab_cap));
+}
+// the per-record buffers of a call of n records, cleared for it
+int echo_reserve(kwok_engine* e, size_t n) {
+    auto& E = e->echo;
+    int rc = 0;
+    if (n > E.cap) {
+        dfree(E.uoff), dfree(E.roff), dfree(E.own), dfree(E.cnt), dfree(E.fill), dfree(E.lbase), dfree(E.list), dfree(E.fidx);
+        dfree(E.bsum), dfree(E.kidx), dfree(E.kpos), dfree(E.q_len), dfree(E.res_rel), dfree(E.ulen), dfree(E.rlen);
+        dfree(E.kind), dfree(E.res), dfree(E.hash), dfree(E.q_off), dfree(E.hdrop), dfree(E.res_h), dfree(E.res_st);
+        E.cap = 0;
+        const size_t cap = std::max<size_t>(n + n / 4, 4096);
+        if ((rc = dalloc(e, &E.uoff, cap)) || (rc = dalloc(e, &E.roff, cap)) || (rc = dalloc(e, &E.own, cap)) ||
+            (rc = dalloc(e, &E.cnt, cap)) || (rc = dalloc(e, &E.fill, cap)) || (rc = dalloc(e, &E.lbase, cap)) ||
+            (rc = dalloc(e, &E.list, cap)) || (rc = dalloc(e, &E.fidx, cap)) || (rc = dalloc(e, &E.bsum, cap / 256 + 2)) ||
+            (rc = dalloc(e, &E.kidx, cap)) || (rc = dalloc(e, &E.kpos, cap)) || (rc = dalloc(e, &E.q_len, cap)) ||
+            (rc = dalloc(e, &E.res_rel, cap)) || (rc = dalloc(e, &E.ulen, cap)) || (rc = dalloc(e, &E.rlen, cap)) ||
+            (rc = dalloc(e, &E.kind, cap)) || (rc = dalloc(e, &E.res, cap)) || (rc = dalloc(e, &E.hash, cap)) ||
+            (rc = dalloc(e, &E.q_off, cap)) || (rc = dalloc(e, &E.hdrop, cap)) || (rc = dalloc(e, &E.res_h, cap)) ||
+            (rc = dalloc(e, &E.res_st, cap)))
+            return rc;
+        E.cap = cap;
+    }
+    size_t ccap = 64;
+    while (ccap < 2 * n) ccap <<= 1;
+    if (ccap > E.claim_cap) {
+        dfree(E.claim);
+        E.claim_cap = 0;
+        if ((rc = dalloc(e, &E.claim, ccap))) return rc;
+        E.claim_cap = ccap;
+    }
+    hipStream_t st = e->st;
+    HIPCHK(e, hipMemsetAsync(E.claim, 0xFF, ccap * 4, st));
+    HIPCHK(e, hipMemsetAsync(E.cnt, 0, n * 4, st));
+    HIPCHK(e, hipMemsetAsync(E.fill, 0, n * 4, st));
+    HIPCHK(e, hipMemsetAsync(E.call, 0, sizeof(EchoCall), st));
+    return KWOK_OK;
+}
+EchoBatch echo_batch(kwok_engine* e, const uint8_t* base, uint64_t base_len, size_t n) {
+    auto& E = e->echo;
+    size_t ccap = 64;
+    while (ccap < 2 * n) ccap <<= 1;
+    EchoBatch B{};
+    B.base = base, B.base_len = base_len, B.n = (uint32_t)n;
+    B.uoff = E.uoff, B.roff = E.roff, B.ulen = E.ulen, B.rlen = E.rlen, B.hash = E.hash, B.kind = E.kind, B.res = E.res;
+    B.claim = E.claim, B.claim_mask = (uint32_t)(ccap - 1);
+    B.own = E.own, B.cnt = E.cnt, B.fill = E.fill, B.lbase = E.lbase, B.list = E.list;
+    B.call = E.call;
+    return B;
+}
+// the typed front end's spans and the bytes they name on the device (the arena's used prefix: *arena_len)
+int echo_upload(kwok_engine* e, const uint8_t* op, const char* arena, const uint64_t* uid_off, const uint32_t* uid_len,
+                const uint64_t* rv_off, const uint32_t* rv_len, size_t n, uint64_t* arena_len, EchoSpans* P) {
+    auto& E = e->echo;
+    uint64_t al = 0;
+    for (size_t i = 0; i < n; i++) {  // (a span past 2^32 names no byte of the upload: the device refuses it)
+        if (uid_len[i] && uid_len[i] <= KWOK_UID_MAX && uid_off[i] < 0xFFFFFF00ull) al = std::max<uint64_t>(al, uid_off[i] + uid_len[i]);
+        if (rv_len[i] && rv_len[i] <= KWOK_RV_MAX && rv_off[i] < 0xFFFFFF00ull) al = std::max<uint64_t>(al, rv_off[i] + rv_len[i]);
+    }
+    if (al && !arena) return KWOK_EINVAL;
+    int rc = 0;
+    if (n > E.scap) {
+        dfree(E.s_uoff), dfree(E.s_roff), dfree(E.s_ulen), dfree(E.s_rlen), dfree(E.s_op), dfree(E.s_status);
+        E.scap = 0;
+        const size_t cap = std::max<size_t>(n + n / 4, 4096);
+        if ((rc = dalloc(e, &E.s_uoff, cap)) || (rc = dalloc(e, &E.s_roff, cap)) || (rc = dalloc(e, &E.s_ulen, cap)) ||
+            (rc = dalloc(e, &E.s_rlen, cap)) || (rc = dalloc(e, &E.s_op, cap)) || (rc = dalloc(e, &E.s_status, cap)))
+            return rc;
+        E.scap = cap;
+    }
+    if (al + 1 > E.acap) {
+        dfree(E.arena);
+        E.acap = 0;
+        const size_t cap = std::max<size_t>(al + al / 4 + 1, 1 << 16);
+        if ((rc = dalloc(e, &E.arena, cap))) return rc;
+        E.acap = cap;
+    }
+    hipStream_t st = e->st;
+    HIPCHK(e, hipMemcpyAsync(E.s_uoff, uid_off, n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(E.s_roff, rv_off, n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(E.s_ulen, uid_len, n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(E.s_rlen, rv_len, n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(E.s_op, op, n, hipMemcpyHostToDevice, st));
+    if (al) HIPCHK(e, hipMemcpyAsync(E.arena, arena, al, hipMemcpyHostToDevice, st));
+    *arena_len = al;
+    *P = EchoSpans{E.s_uoff, E.s_roff, E.s_ulen, E.s_rlen, E.s_op};
+    return KWOK_OK;
+}
+// the checks every echo entry makes before it touches anything
+int echo_enter(kwok_engine* e, const char* who) {
+    if (e->poisoned) return poisoned(e);
+    if (!e->echo.on) return e->fail(KWOK_EINVAL, "%s: the echo ledger is not enabled", who);
+    drain(e);
+    if (e->poisoned) return poisoned(e);
+    return KWOK_OK;
+}
+// the filter over all frames of a batch; on return the call's counts are on the host, the kept
+// records' frame indices (E.kidx, E.call_h->n_keep of them) and each record's answer on the device
+int echo_filter_frames(kwok_engine* e, const uint32_t* frame_idx, size_t n, EchoBatch* Bo, EchoFrames* Fo, EchoKeep* Ko) {
+    auto& E = e->echo;
+    auto& Wt = e->watch;
+    hipStream_t st = e->st;
+    int rc = echo_reserve(e, n);
+    if (rc) return rc;
+    HIPCHK(e, hipMemcpyAsync(E.fidx, frame_idx, n * 4, hipMemcpyHostToDevice, st));
+    const EchoBatch B = echo_batch(e, Wt.stream, Wt.len, n);
+    const EchoFrames F{Wt.frames, (uint32_t)Wt.frames_h.size(), E.fidx};
+    const EchoKeep K{E.bsum, E.kidx, E.kpos, E.q_off, E.q_len};
+    hipEvent_t pev[2] = {};
+    if (e->iprof)
+        for (auto& x : pev) (void)hipEventCreate(&x);
+    if (pev[0]) (void)hipEventRecord(pev[0], st);
+    launch_echo_key_frames(B, F, st);
+    launch_echo_group(B, st);
+    launch_echo_decide(E.ledger(), B, st);
+    launch_echo_keep(B, F, K, st);
+    if (pev[1]) (void)hipEventRecord(pev[1], st);
+    HIPCHK(e, hipGetLastError());
+    rc = echo_read(e, true);
+    if (pev[0] && pev[1]) {
+        float ms = 0;
+        if (!rc && hipEventElapsedTime(&ms, pev[0], pev[1]) == hipSuccess)
+            fprintf(stderr, "[kwok echo] %zu frames, %u echoes, %u repeats: the echo kernels %.3f ms\n", n, E.call_h->n_drop,
+                    E.call_h->n_rep, ms);
+    }
+    for (auto& x : pev)
+        if (x) (void)hipEventDestroy(x);
+    if (rc) return rc;
+    if (E.call_h->n_keep > n) return e->fail(KWOK_EDEVICE, "echo ledger: %u of %zu records kept", E.call_h->n_keep, n);
+    *Bo = B, *Fo = F, *Ko = K;
+    return KWOK_OK;
+}
+}  // namespace
+
+int kwok_echo_enable(kwok_engine* e) {
+    if (!e) return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    if (e->multi) return e->fail(KWOK_EINVAL, "kwok_echo_enable: single-rank engines only");
+    auto& E = e->echo;
+    if (E.on) return KWOK_OK;
+    if (const char* v = getenv("KWOK_ECHO_TAB_LOG2")) {
+        const int l = atoi(v);
+        if (l < 4 || l > 31) return e->fail(KWOK_EINVAL, "KWOK_ECHO_TAB_LOG2 must be 4..31");
+        E.forced_log2 = l;
+    }
+    int rc = 0;  // (dalloc zeroes: an empty table, no note)
+    if (!E.ctr) {
+        if ((rc = dalloc(e, &E.ctr, 1)) || (rc = dalloc(e, &E.call, 1))) return rc;
+        if (hipHostMalloc((void**)&E.ctr_h, sizeof(EchoCounters), hipHostMallocDefault) != hipSuccess ||
+            hipHostMalloc((void**)&E.call_h, sizeof(EchoCall), hipHostMallocDefault) != hipSuccess)
+            return e->fail(KWOK_ENOMEM, "echo ledger staging");
+        memset(E.ctr_h, 0, sizeof(EchoCounters));
+        memset(E.call_h, 0, sizeof(EchoCall));
+    }
+    if (!E.tab) {
+        const size_t cap = E.forced_log2 ? (size_t)1 << E.forced_log2 : 64;
+        const size_t pcap = E.forced_log2 ? cap - 1 : cap / 2;
+        if ((rc = dalloc(e, &E.tab, cap))) return rc;
+        if ((rc = dalloc(e, &E.pool, pcap))) return rc;
+        E.tab_cap = cap, E.pool_cap = pcap;
+    }
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    E.on = true;
+    return KWOK_OK;
+}
+
+int kwok_echo_update(kwok_engine* e, const uint8_t* op, const char* arena, const uint64_t* uid_off,
+                     const uint32_t* uid_len, const uint64_t* rv_off, const uint32_t* rv_len, size_t n,
+                     int32_t* out_status) {
+    if (!e || (n && (!op || !uid_off || !uid_len || !rv_off || !rv_len)) || n > 0x7FFFFFF0ull) return KWOK_EINVAL;
+    int rc = echo_enter(e, "kwok_echo_update");
+    if (rc) return rc;
+    if (!n) return 0;
+    auto& E = e->echo;
+    uint64_t al = 0;
+    EchoSpans P{};
+    if ((rc = echo_upload(e, op, arena, uid_off, uid_len, rv_off, rv_len, n, &al, &P))) return rc;
+    if ((rc = echo_reserve(e, n))) return rc;
+    hipStream_t st = e->st;
+    const EchoBatch B = echo_batch(e, E.arena, al, n);
+    launch_echo_key_update(B, P, E.s_status, st);
+    launch_echo_group(B, st);
+    launch_echo_need(E.ledger(), B, st);
+    HIPCHK(e, hipGetLastError());
+    // the room the call needs, before anything is stored: compacted, grown or refused here
+    if ((rc = echo_read(e, true)) || (rc = echo_ensure(e, E.call_h->n_new))) return rc;
+    launch_echo_update(E.ledger(), B, st);
+    HIPCHK(e, hipGetLastError());
+    if (out_status) HIPCHK(e, hipMemcpyAsync(out_status, E.s_status, n * 4, hipMemcpyDeviceToHost, st));
+    if ((rc = echo_read(e, true))) return rc;
+    return (int)E.call_h->n_bad;
+}
+
+int kwok_echo_match(kwok_engine* e, const char* arena, const uint64_t* uid_off, const uint32_t* uid_len,
+                    const uint64_t* rv_off, const uint32_t* rv_len, const uint8_t* deleted, size_t n,
+                    uint8_t* out_drop) {
+    if (!e || (n && (!uid_off || !uid_len || !rv_off || !rv_len || !deleted || !out_drop)) || n > 0x7FFFFFF0ull)
+        return KWOK_EINVAL;
+    int rc = echo_enter(e, "kwok_echo_match");
+    if (rc) return rc;
+    if (!n) return KWOK_OK;
+    auto& E = e->echo;
+    uint64_t al = 0;
+    EchoSpans P{};
+    if ((rc = echo_upload(e, deleted, arena, uid_off, uid_len, rv_off, rv_len, n, &al, &P))) return rc;
+    if ((rc = echo_reserve(e, n))) return rc;
+    hipStream_t st = e->st;
+    const EchoBatch B = echo_batch(e, E.arena, al, n);
+    launch_echo_key_typed(B, P, st);
+    launch_echo_group(B, st);
+    launch_echo_decide(E.ledger(), B, st);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(out_drop, E.res, n, hipMemcpyDeviceToHost, st));  // (ER_KEEP 0, ER_DROP 1)
+    return echo_read(e, true);
+}
+
+int kwok_ingest_pods_framed_echo(kwok_engine* e, const kwok_codec* c, uint64_t stream_id, const uint32_t* frame_idx,
+                                 size_t n, int32_t* out_handles, int32_t* out_status, uint32_t* out_released,
+                                 size_t* n_host, size_t* n_runs, size_t* n_echoes) {
+    if (n_host) *n_host = 0;
+    if (n_runs) *n_runs = 0;
+    if (n_echoes) *n_echoes = 0;
+    if (!e || !c || (n && !frame_idx) || n > 0x7FFFFFF0ull) return KWOK_EINVAL;
+    int rc = echo_enter(e, "kwok_ingest_pods_framed_echo");
+    if (rc) return rc;
+    auto& E = e->echo;
+    auto& U = e->uid;
+    auto& Wt = e->watch;
+    if (!U.on) return e->fail(KWOK_EINVAL, "kwok_ingest_pods_framed_echo: the uid directory is not enabled");
+    if (!stream_id || stream_id != Wt.id) return e->fail(KWOK_EINVAL, "stream_id is not the resident watch stream");
+    if (!n) return 0;
+    hipStream_t st = e->st;
+    EchoBatch B{};
+    EchoFrames F{};
+    EchoKeep K{};
+    if ((rc = echo_filter_frames(e, frame_idx, n, &B, &F, &K))) return rc;
+    const size_t nk = E.call_h->n_keep, nd = E.call_h->n_drop;
+    if (nd) {  // the echoes' live handles, before the kept records change anything
+        if ((rc = uid_ensure(e, 0))) return rc;
+        launch_uid_lookup(e->S, U.dir(), Wt.stream, Wt.len, K.q_off, K.q_len, (uint32_t)n, E.hdrop, st);
+        HIPCHK(e, hipGetLastError());
+    }
+    if (nk && (rc = pods_framed_uid_impl(e, c, stream_id, nullptr, E.kidx, nk, nullptr, nullptr, nullptr, n_host, n_runs)) < 0)
+        return rc;
+    // (no kept record: k_echo_fix reads no result of the ingest)
+    launch_echo_fix(B, K, E.hdrop, nk ? U.res_h : E.res_h, nk ? U.res_st : E.res_st, nk ? U.res_rel : E.res_rel, E.res_h, E.res_st,
+                    E.res_rel, st);
+    HIPCHK(e, hipGetLastError());
+    if (out_handles) HIPCHK(e, hipMemcpyAsync(out_handles, E.res_h, n * 4, hipMemcpyDeviceToHost, st));
+    if (out_released) HIPCHK(e, hipMemcpyAsync(out_released, E.res_rel, n * 4, hipMemcpyDeviceToHost, st));
+    std::vector<int32_t> st_tmp(out_status ? 0 : n);
+    int32_t* sts = out_status ? out_status : st_tmp.data();
+    HIPCHK(e, hipMemcpyAsync(sts, E.res_st, n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    int rejected = 0;
+    for (size_t i = 0; i < n; i++) rejected += sts[i] != KWOK_OK && sts[i] != KWOK_NOT_SENT && sts[i] != KWOK_ECHO;
+    if (n_echoes) *n_echoes = nd;
+    return rejected;
+}
+
+int kwok_ingest_nodes_framed_echo(kwok_engine* e, const kwok_codec* c, uint64_t stream_id, const uint32_t* frame_idx,
+                                  size_t n, int32_t* out_handles, int32_t* out_status, size_t* n_host,
+                                  size_t* n_echoes) {
+    if (n_host) *n_host = 0;
+    if (n_echoes) *n_echoes = 0;
+    if (!e || !c || (n && !frame_idx) || n > 0x7FFFFFF0ull) return KWOK_EINVAL;
+    int rc = echo_enter(e, "kwok_ingest_nodes_framed_echo");
+    if (rc) return rc;
+    auto& E = e->echo;
+    auto& Wt = e->watch;
+    if (!stream_id || stream_id != Wt.id) return e->fail(KWOK_EINVAL, "stream_id is not the resident watch stream");
+    if (!n) return 0;
+    hipStream_t st = e->st;
+    EchoBatch B{};
+    EchoFrames F{};
+    EchoKeep K{};
+    if ((rc = echo_filter_frames(e, frame_idx, n, &B, &F, &K))) return rc;
+    const size_t nk = E.call_h->n_keep, nd = E.call_h->n_drop;
+    // the node ingest takes its records from the host: the kept indices come back (4 bytes per kept
+    // record), with every record's answer (1 byte) and, if any, the echoes' handles
+    std::vector<uint32_t> kidx(nk), kpos(n);
+    std::vector<uint8_t> res(n);
+    std::vector<int32_t> hdrop(nd ? n : 0);
+    if (nd) {
+        launch_echo_node_handles(e->S, B, F, E.hdrop, st);
+        HIPCHK(e, hipGetLastError());
+        HIPCHK(e, hipMemcpyAsync(hdrop.data(), E.hdrop, n * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (nk) HIPCHK(e, hipMemcpyAsync(kidx.data(), E.kidx, nk * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipMemcpyAsync(kpos.data(), E.kpos, n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipMemcpyAsync(res.data(), E.res, n, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    std::vector<int32_t> kh(nk), ks(nk);
+    if (nk && (rc = kwok_ingest_nodes_framed(e, c, stream_id, kidx.data(), nk, kh.data(), ks.data(), n_host)) < 0) return rc;
+    int rejected = 0;
+    for (size_t i = 0; i < n; i++) {
+        int32_t h = -1, s = KWOK_EINVAL;
+        if (res[i] == ER_KEEP && kpos[i] < nk) h = kh[kpos[i]], s = ks[kpos[i]];
+        else if (res[i] == ER_DROP) h = hdrop[i], s = KWOK_ECHO;
+        else if (res[i] == ER_EDOMAIN) s = KWOK_EDOMAIN;
+        if (out_handles) out_handles[i] = h;
+        if (out_status) out_status[i] = s;
+        rejected += s != KWOK_OK && s != KWOK_ECHO;
+    }
+    if (n_echoes) *n_echoes = nd;
+    return rejected;
+}
+
+int kwok_echo_stats(kwok_engine* e, uint64_t out[KWOK_ECHO_STAT_COUNT]) {
+    if (!e || !out) return KWOK_EINVAL;
+    auto& E = e->echo;
+    for (int k = 0; k < KWOK_ECHO_STAT_COUNT; k++) out[k] = 0;
+    if (!E.ctr_h) return KWOK_OK;
+    out[KWOK_ECHO_STAT_NOTES] = E.ctr_h->notes;
+    out[KWOK_ECHO_STAT_FORGETS] = E.ctr_h->forgets;
+    out[KWOK_ECHO_STAT_EVICTIONS] = E.ctr_h->evictions;
+    out[KWOK_ECHO_STAT_MATCHED] = E.ctr_h->matched;
+    out[KWOK_ECHO_STAT_DROPPED] = E.ctr_h->dropped;
+    out[KWOK_ECHO_STAT_KEPT_MATCHED] = E.ctr_h->kept_matched;
+    out[KWOK_ECHO_STAT_REBUILDS] = E.rebuilds;
+    out[KWOK_ECHO_STAT_LIVE_UIDS] = E.ctr_h->live;
+    out[KWOK_ECHO_STAT_TABLE_ENTRIES] = E.ctr_h->used;
     return KWOK_OK;
 }
 

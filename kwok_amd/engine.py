@@ -130,6 +130,12 @@ def declare(lib, pre):
             "uid_lookup": (C.c_int, [VP, VP, VP, VP, SZ, VP]),
             "ingest_pods_framed_uid": (C.c_int, [VP, VP, U64, VP, SZ, VP, VP, VP, P(SZ), P(SZ)]),
             "uid_stats": (C.c_int, [VP, VP]),
+            "echo_enable": (C.c_int, [VP]),
+            "echo_update": (C.c_int, [VP, VP, VP, VP, VP, VP, VP, SZ, VP]),
+            "echo_match": (C.c_int, [VP, VP, VP, VP, VP, VP, VP, SZ, VP]),
+            "ingest_pods_framed_echo": (C.c_int, [VP, VP, U64, VP, SZ, VP, VP, VP, P(SZ), P(SZ), P(SZ)]),
+            "ingest_nodes_framed_echo": (C.c_int, [VP, VP, U64, VP, SZ, VP, VP, P(SZ), P(SZ)]),
+            "echo_stats": (C.c_int, [VP, VP]),
         })
     for name, (res, args) in sig.items():
         f = getattr(lib, pre + name, None)
@@ -764,6 +770,79 @@ class Engine(EngineBase):
         out = (C.c_uint64 * len(abi.UID_STATS))()
         self._check(self._lib.kwok_uid_stats(self._h, out), "uid_stats")
         return dict(zip(abi.UID_STATS, list(out)))
+
+    # ---- the echo ledger (include/kwok_watch.h): own-patch echoes dropped on the device ----
+    @staticmethod
+    def _echo_spans(uids, rvs):
+        """uids, rvs (bytes, str or None each) -> (arena, uid offsets, uid lengths, rv offsets, rv lengths)"""
+        enc = lambda x: b"" if x is None else x.encode() if isinstance(x, str) else bytes(x)  # noqa: E731
+        ub, rb = [enc(u) for u in uids], [enc(r) for r in rvs]
+        assert len(ub) == len(rb)
+        n = len(ub)
+        lens = np.fromiter((len(b) for b in ub + rb), np.uint32, 2 * n)
+        offs = np.zeros(2 * n, np.uint64)
+        if n:
+            np.cumsum(lens[:-1], out=offs[1:])
+        arena = np.frombuffer(b"".join(ub + rb) + b"\0", np.uint8)
+        return arena, offs[:n].copy(), lens[:n].copy(), offs[n:].copy(), lens[n:].copy()
+
+    def echo_enable(self):
+        """kwok_echo_enable: allocate the ledger (idempotent; single-rank engines only)"""
+        self._check(self._lib.kwok_echo_enable(self._h), "echo_enable")
+
+    def echo_update(self, ops, uids, rvs):
+        """kwok_echo_update: ops[i] (abi.ECHO_NOTE / ECHO_FORGET) on (uids[i], rvs[i]), in array order
+        per uid -> the per-op statuses"""
+        op = np.ascontiguousarray(ops, np.uint8)
+        arena, uo, ul, ro, rl = self._echo_spans(uids, rvs)
+        assert len(op) == len(ul)
+        st = np.empty(len(op), np.int32)
+        rc = self._lib.kwok_echo_update(self._h, op.ctypes.data, arena.ctypes.data, uo.ctypes.data, ul.ctypes.data,
+                                        ro.ctypes.data, rl.ctypes.data, len(op), st.ctypes.data)
+        self._check(rc, "echo_update")
+        return st
+
+    def echo_match(self, uids, rvs, deleted):
+        """kwok_echo_match: the filter over typed events -> the drop mask (1: a dropped echo)"""
+        dl = np.ascontiguousarray(deleted, np.uint8)
+        arena, uo, ul, ro, rl = self._echo_spans(uids, rvs)
+        assert len(dl) == len(ul)
+        out = np.zeros(len(dl), np.uint8)
+        rc = self._lib.kwok_echo_match(self._h, arena.ctypes.data, uo.ctypes.data, ul.ctypes.data, ro.ctypes.data,
+                                       rl.ctypes.data, dl.ctypes.data, len(dl), out.ctypes.data)
+        self._check(rc, "echo_match")
+        return out
+
+    def ingest_pods_framed_echo(self, codec, stream_id, frame_idx):
+        """kwok_ingest_pods_framed_echo over ALL frames of a batch: (handles, statuses, released,
+        documents the host decided, runs, echoes dropped)"""
+        idx = np.ascontiguousarray(frame_idx, np.uint32)
+        n = len(idx)
+        hs, st, rel = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.uint32)
+        nh, nr, ne = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        rc = self._lib.kwok_ingest_pods_framed_echo(self._h, codec._h, stream_id, idx.ctypes.data, n, hs.ctypes.data,
+                                                    st.ctypes.data, rel.ctypes.data, C.byref(nh), C.byref(nr), C.byref(ne))
+        self._check(rc, "ingest_pods_framed_echo")
+        return hs, st, rel, nh.value, nr.value, ne.value
+
+    def ingest_nodes_framed_echo(self, codec, stream_id, frame_idx):
+        """kwok_ingest_nodes_framed_echo over ALL frames of a batch: (handles, statuses, documents the
+        host decided, echoes dropped)"""
+        idx = np.ascontiguousarray(frame_idx, np.uint32)
+        n = len(idx)
+        hs, st = np.empty(n, np.int32), np.empty(n, np.int32)
+        nh, ne = C.c_size_t(), C.c_size_t()
+        rc = self._lib.kwok_ingest_nodes_framed_echo(self._h, codec._h, stream_id, idx.ctypes.data, n, hs.ctypes.data,
+                                                     st.ctypes.data, C.byref(nh), C.byref(ne))
+        self._check(rc, "ingest_nodes_framed_echo")
+        return hs, st, nh.value, ne.value
+
+    def echo_stats(self):
+        """kwok_echo_stats: notes / forgets / evictions / matched / dropped / kept after a match / rebuilds /
+        live uids / table entries"""
+        out = (C.c_uint64 * len(abi.ECHO_STATS))()
+        self._check(self._lib.kwok_echo_stats(self._h, out), "echo_stats")
+        return dict(zip(abi.ECHO_STATS, list(out)))
 
     @staticmethod
     def _arena_arg(arena):
