@@ -365,6 +365,83 @@ enum {
 };
 int kwok_echo_stats(kwok_engine* e, uint64_t out[KWOK_ECHO_STAT_COUNT]);
 
+/* ---- Pod and node reference directory ---------------------------
+ *
+ * What a patch is addressed to - a pod's namespace, name and uid, a node's name - kept
+ * on the device and handed back in the order of the tick's output lists, so a caller
+ * keeps no per-object map for addressing.
+ *
+ * Rules:
+ *   - per pod slot the namespace and the name (opaque bytes: namespace <= 63, name
+ *     1..253) are stored; the uid is the uid directory's; a node's name is the node
+ *     directory's (nodes carry no namespace and no uid here);
+ *   - while the directory is on, every pod create (an UPSERT without a handle whose
+ *     final status is KWOK_OK) through a by-uid entry (kwok_ingest_pods_framed_uid,
+ *     kwok_ingest_pods_framed_echo) stores its frame's namespace and name from the
+ *     resident stream; a frame with KWOK_FRAME_ESC_NAME / _NS, an empty name, a name
+ *     over 253 bytes or a namespace over 63 stores none (never truncated or guessed).
+ *     A create through any other entry stores none: a reused slot never keeps its
+ *     previous pod's name.  An upsert of a known pod stores nothing;
+ *   - kwok_refs_bind names the pods that have none (typed events, records, escaped
+ *     frames whose decoded text the caller holds);
+ *   - whatever frees a slot (a Deleted event, the tick, a sweep) leaves its bytes:
+ *     KWOK_REFS_DELETE and KWOK_REFS_ANY_SLOT answer from them until the slot is
+ *     created into again;
+ *   - stale guard: every call that can create an object of a kind (its ingest entries,
+ *     kwok_refs_bind for pods) moves that kind's counter; kwok_read_refs refuses a
+ *     list of a kind whose counter moved since the collected tick's submit
+ *     (KWOK_EINVAL; kwok_last_error says so).  Flush, tick, apply never trips it;
+ *   - single-rank engines only.
+ *
+ * Output: refs[i] describes item i; its bytes are namespace, name, uid, concatenated
+ * at blob + refs[i].off.  Every off is a multiple of 16, items lie in list order and
+ * an item's tail is zero up to the next multiple of 16; *blob_used is the total.
+ * blob_cap below the total: KWOK_EINVAL, *blob_used set to the need, nothing
+ * written. */
+#define KWOK_REF_NS_MAX 63
+#define KWOK_REF_NAME_MAX 253
+#define KWOK_REF_STRIDE 320 /* bytes per pod slot: 63 + 253 rounded up to 16-byte units */
+#define KWOK_REF_NONE 3     /* kwok_ref.status: a live pod with no name stored */
+#define KWOK_REFS_ANY_SLOT 1 /* kwok_refs_lookup flag: what the slot last stored, live or not */
+typedef struct kwok_ref {
+    uint64_t off;                     /* into blob, a multiple of 16 */
+    uint8_t ns_len, name_len, uid_len;
+    int8_t status;                    /* KWOK_OK / KWOK_ENOTFOUND / KWOK_REF_NONE (lengths 0, the uid given if known) */
+    uint32_t reserved0;
+} kwok_ref;
+enum { KWOK_REFS_HEARTBEAT = 0, KWOK_REFS_NODE_INIT, KWOK_REFS_POD_PATCH, KWOK_REFS_DELETE, KWOK_REFS_LIST_COUNT };
+/* Allocates the directory and enables the uid directory (idempotent).  Pods that exist
+ * have no name until bound.  KWOK_EINVAL on a multi-rank engine. */
+int kwok_refs_enable(kwok_engine* e);
+/* namespace i = arena[ns_off[i], +ns_len[i]) and name i = arena[name_off[i], +name_len[i])
+ * become those of live pod handles[i] (rebinding replaces them).  Counted in *n_bad,
+ * storing nothing: a handle out of range or on an unused slot, an empty name, a name over
+ * KWOK_REF_NAME_MAX, a namespace over KWOK_REF_NS_MAX.  One handle named twice in a call is the caller's error
+ * (its record then holds 16-byte units of either).  Drains submitted ticks first. */
+int kwok_refs_bind(kwok_engine* e, const int32_t* handles, const char* arena, const uint64_t* ns_off,
+                   const uint32_t* ns_len, const uint64_t* name_off, const uint32_t* name_len, size_t n, size_t* n_bad);
+/* The references of handles[0, n) of `kind` (KWOK_KIND_PODS / KWOK_KIND_NODES) in the
+ * caller's order.  A handle out of range or not live: KWOK_ENOTFOUND, all lengths 0;
+ * with KWOK_REFS_ANY_SLOT a handle in range answers what its slot last stored (ask
+ * before the next ingest of that kind).  Drains submitted ticks first. */
+int kwok_refs_lookup(kwok_engine* e, int kind, const int32_t* handles, size_t n, uint32_t flags, kwok_ref* refs,
+                     char* blob, size_t blob_cap, size_t* blob_used);
+/* Items [first, first + count) of output list `which` (KWOK_REFS_*) of the last collected
+ * tick, read on the device (no handle is uploaded).  A range outside the list, no
+ * collected tick, or a moved counter (the stale guard): KWOK_EINVAL. */
+int kwok_read_refs(kwok_engine* e, int which, size_t first, size_t count, kwok_ref* refs, char* blob, size_t blob_cap,
+                   size_t* blob_used);
+enum {
+    KWOK_REFS_STAT_BINDS = 0, /* names stored by kwok_refs_bind */
+    KWOK_REFS_STAT_NOTES,     /* names stored by ingests (creates through a by-uid entry) */
+    KWOK_REFS_STAT_UNNAMED,   /* creates stored without a name */
+    KWOK_REFS_STAT_READS,     /* references read (kwok_refs_lookup and kwok_read_refs items) */
+    KWOK_REFS_STAT_NOT_FOUND, /* ... of them KWOK_ENOTFOUND */
+    KWOK_REFS_STAT_BYTES,     /* device memory the directory holds (the uid directory's not included) */
+    KWOK_REFS_STAT_COUNT
+};
+int kwok_refs_stats(kwok_engine* e, uint64_t out[KWOK_REFS_STAT_COUNT]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,10 @@ type gpuEngine struct {
 	h       *C.kwok_engine
 	hb      []int32 // heartbeat handle list of heartbeat epoch hbEpoch
 	hbEpoch uint32
+	// refDir (KWOK_REF_DIR=1): the engine's reference directory (kwok_watch.h, DESIGN.md §25) hands every
+	// body's addressee back in list order; hbRefs: the heartbeat list's references of epoch hbEpoch
+	refDir bool
+	hbRefs []objRef
 	// page-locked batch buffers (kwok_host_alloc), reused: kwok_ingest_pods reads
 	// the records and strings in place from these (batches over KWOK_INGEST_CHUNK
 	// records: copied by DMA, chunk by chunk), and writes the per-record results to
@@ -647,6 +651,109 @@ func (g *gpuEngine) ingestPodsFramedUID(codec *gpuCodec, streamID uint64, idx []
 	return handles, status, int(nr), err
 }
 
+// ---- the pod and node reference directory (kwok_watch.h, DESIGN.md §25) ----
+
+// objRef: one kwok_ref with its bytes - what a patch is addressed to
+type objRef struct {
+	status               int8 // C.KWOK_OK, C.KWOK_ENOTFOUND or C.KWOK_REF_NONE (no name stored)
+	namespace, name, uid string
+}
+
+const refsPiece = 1 << 16 // references read per kwok_read_refs call at most
+
+// refsEnable: kwok_refs_enable (idempotent; it enables the uid directory as well; single-rank engines only)
+func (g *gpuEngine) refsEnable() error {
+	if rc := C.kwok_refs_enable(g.h); rc != C.KWOK_OK {
+		return fmt.Errorf("kwok_refs_enable: %d: %s", int(rc), g.lastError())
+	}
+	g.refDir = true
+	return nil
+}
+
+// refsBind: kwok_refs_bind - (namespaces[i], names[i]) become those of live pod handles[i]; returns the
+// records that stored nothing
+func (g *gpuEngine) refsBind(handles []int32, namespaces, names []string) (int, error) {
+	n := len(handles)
+	if n == 0 {
+		return 0, nil
+	}
+	var arena []byte
+	nsOff, nsLen := make([]uint64, n), make([]uint32, n)
+	nmOff, nmLen := make([]uint64, n), make([]uint32, n)
+	for i := 0; i < n; i++ {
+		nsOff[i], nsLen[i] = uint64(len(arena)), uint32(len(namespaces[i]))
+		arena = append(arena, namespaces[i]...)
+		nmOff[i], nmLen[i] = uint64(len(arena)), uint32(len(names[i]))
+		arena = append(arena, names[i]...)
+	}
+	arena = append(arena, 0)
+	var bad C.size_t
+	rc := C.kwok_refs_bind(g.h, (*C.int32_t)(&handles[0]), (*C.char)(unsafe.Pointer(&arena[0])), (*C.uint64_t)(&nsOff[0]),
+		(*C.uint32_t)(&nsLen[0]), (*C.uint64_t)(&nmOff[0]), (*C.uint32_t)(&nmLen[0]), C.size_t(n), &bad)
+	if rc < 0 {
+		return 0, fmt.Errorf("kwok_refs_bind: %d: %s", int(rc), g.lastError())
+	}
+	return int(bad), nil
+}
+
+// refsCall: one kwok_refs_lookup / kwok_read_refs of n items; a blob that proved too small is asked for
+// again with the size the call reported
+func (g *gpuEngine) refsCall(what string, n int, call func(refs *C.kwok_ref, blob *C.char, cap C.size_t, used *C.size_t) C.int) ([]objRef, error) {
+	if n == 0 {
+		return nil, nil
+	}
+	refs := make([]C.kwok_ref, n)
+	blob := make([]byte, 64*n+16)
+	var used C.size_t
+	rc := call(&refs[0], (*C.char)(unsafe.Pointer(&blob[0])), C.size_t(len(blob)), &used)
+	if rc == C.KWOK_EINVAL && int(used) > len(blob) {
+		blob = make([]byte, int(used))
+		rc = call(&refs[0], (*C.char)(unsafe.Pointer(&blob[0])), C.size_t(len(blob)), &used)
+	}
+	if rc != C.KWOK_OK {
+		return nil, fmt.Errorf("%s: %d: %s", what, int(rc), g.lastError())
+	}
+	out := make([]objRef, n)
+	for i := range refs {
+		r := &refs[i]
+		o, a, b, c := int(r.off), int(r.ns_len), int(r.name_len), int(r.uid_len)
+		out[i] = objRef{status: int8(r.status), namespace: string(blob[o : o+a]), name: string(blob[o+a : o+a+b]),
+			uid: string(blob[o+a+b : o+a+b+c])}
+	}
+	return out, nil
+}
+
+// refsLookup: kwok_refs_lookup - the references of handles (C.KWOK_KIND_PODS / _NODES) in the caller's order;
+// flags: C.KWOK_REFS_ANY_SLOT for handles the engine has just freed (a sweep's removed list)
+func (g *gpuEngine) refsLookup(kind int, handles []int32, flags uint32) ([]objRef, error) {
+	if len(handles) == 0 {
+		return nil, nil
+	}
+	return g.refsCall("kwok_refs_lookup", len(handles), func(refs *C.kwok_ref, blob *C.char, cap C.size_t, used *C.size_t) C.int {
+		return C.kwok_refs_lookup(g.h, C.int(kind), (*C.int32_t)(&handles[0]), C.size_t(len(handles)), C.uint32_t(flags), refs, blob, cap, used)
+	})
+}
+
+// readRefs: kwok_read_refs - items [first, first+count) of list `which` (C.KWOK_REFS_*) of the collected
+// tick, in pieces of refsPiece
+func (g *gpuEngine) readRefs(which, first, count int) ([]objRef, error) {
+	out := make([]objRef, 0, count)
+	for lo := first; lo < first+count; lo += refsPiece {
+		cnt := first + count - lo
+		if cnt > refsPiece {
+			cnt = refsPiece
+		}
+		part, err := g.refsCall("kwok_read_refs", cnt, func(refs *C.kwok_ref, blob *C.char, cap C.size_t, used *C.size_t) C.int {
+			return C.kwok_read_refs(g.h, C.int(which), C.size_t(lo), C.size_t(cnt), refs, blob, cap, used)
+		})
+		if err != nil {
+			return nil, err
+		}
+		out = append(out, part...)
+	}
+	return out, nil
+}
+
 // ---- the echo ledger (kwok_watch.h, DESIGN.md §24) ----
 const (
 	echoNote   = uint8(C.KWOK_ECHO_NOTE)
@@ -771,8 +878,10 @@ func finalizerPatch() []byte {
 // once, straight into Go memory (the engine keeps no pointer past the call).  A
 // steady tick at 1M nodes moves ~1 KB over PCIe, not 1 GB.  The heartbeat handle
 // list is read only when its epoch changed.  Body slices stay valid after tick
-// returns (each aliases its piece's buffer).
-func (g *gpuEngine) tick(nowUnix int64, apply func(kind int, handle int32, body []byte)) error {
+// returns (each aliases its piece's buffer).  ref (refDir): the addressee the device hands back for the
+// body - the lists' references are read beside the arena pieces, the heartbeat list's with its handle
+// list, the delete list's before any apply (the tick freed those pods, their bytes stay); nil otherwise.
+func (g *gpuEngine) tick(nowUnix int64, apply func(kind int, handle int32, body []byte, ref *objRef)) error {
 	var res C.kwok_tick_result
 	if rc := C.kwok_tick(g.h, C.int64_t(nowUnix), &res); rc != C.KWOK_OK {
 		return fmt.Errorf("kwok_tick: %s", g.lastError())
@@ -808,26 +917,45 @@ func (g *gpuEngine) tick(nowUnix int64, apply func(kind int, handle int32, body 
 		return fmt.Errorf("kwok_read_outputs: %s", g.lastError())
 	}
 	g.hbEpoch = uint32(res.heartbeat_epoch)
+	if g.refDir && newEpoch { // the heartbeat list's references change with the handle list
+		var err error
+		if g.hbRefs, err = g.readRefs(C.KWOK_REFS_HEARTBEAT, 0, int(res.n_heartbeat)); err != nil {
+			return err
+		}
+	}
+	refOf := func(refs []objRef, i int) *objRef {
+		if !g.refDir {
+			return nil
+		}
+		return &refs[i]
+	}
 	if res.n_heartbeat > 0 {
 		body := make([]byte, res.heartbeat_len) // the heartbeat body, sent to every managed node
 		if err := g.readArena(uint64(out.heartbeat_off), body); err != nil {
 			return err
 		}
-		for _, h := range g.hb {
-			apply(kindHeartbeat, h, body)
+		for i, h := range g.hb {
+			apply(kindHeartbeat, h, body, refOf(g.hbRefs, i))
 		}
 	}
-	if err := g.applyPatches(kindNodeInit, ini, iniOff, iniLen, apply); err != nil {
+	if err := g.applyPatches(kindNodeInit, C.KWOK_REFS_NODE_INIT, ini, iniOff, iniLen, apply); err != nil {
 		return err
 	}
-	if err := g.applyPatches(kindPodPatch, pp, ppOff, ppLen, apply); err != nil {
+	if err := g.applyPatches(kindPodPatch, C.KWOK_REFS_POD_PATCH, pp, ppOff, ppLen, apply); err != nil {
 		return err
+	}
+	var delRefs []objRef
+	if g.refDir {
+		var err error
+		if delRefs, err = g.readRefs(C.KWOK_REFS_DELETE, 0, len(del)); err != nil {
+			return err
+		}
 	}
 	for i, h := range del { // Patch(removeFinalizers) if the pod has finalizers, then Delete(grace 0)
 		if delFin[i] != 0 {
-			apply(kindDeleteFin, h, nil)
+			apply(kindDeleteFin, h, nil, refOf(delRefs, i))
 		} else {
-			apply(kindDelete, h, nil)
+			apply(kindDelete, h, nil, refOf(delRefs, i))
 		}
 	}
 	return nil
@@ -835,8 +963,8 @@ func (g *gpuEngine) tick(nowUnix int64, apply func(kind int, handle int32, body 
 
 // applyPatches: the patches at offs[i] / lens[i] (increasing offsets), read in
 // pieces of at most readChunk bytes (a single larger patch is one piece)
-func (g *gpuEngine) applyPatches(kind int, hs []int32, offs []uint64, lens []uint32,
-	apply func(kind int, handle int32, body []byte)) error {
+func (g *gpuEngine) applyPatches(kind, which int, hs []int32, offs []uint64, lens []uint32,
+	apply func(kind int, handle int32, body []byte, ref *objRef)) error {
 	for i := 0; i < len(hs); {
 		lo := offs[i]
 		j := i + 1
@@ -847,8 +975,19 @@ func (g *gpuEngine) applyPatches(kind int, hs []int32, offs []uint64, lens []uin
 		if err := g.readArena(lo, buf); err != nil {
 			return err
 		}
+		var refs []objRef // (refDir: the piece's references beside its bytes)
+		if g.refDir {
+			var err error
+			if refs, err = g.readRefs(which, i, j-i); err != nil {
+				return err
+			}
+		}
 		for k := i; k < j; k++ {
-			apply(kind, hs[k], buf[offs[k]-lo:offs[k]-lo+uint64(lens[k])])
+			var ref *objRef
+			if g.refDir {
+				ref = &refs[k-i]
+			}
+			apply(kind, hs[k], buf[offs[k]-lo:offs[k]-lo+uint64(lens[k])], ref)
 		}
 		i = j
 	}

@@ -247,6 +247,12 @@ type GPUController struct {
 	// podByUID is then a batch-local map filled by kwok_uid_lookup, and List pages go through
 	// kwok_ingest_pods_framed_uid.  podUID / podRef (handle -> uid / name, for addressing patches) stay
 	byUID       bool
+	// refDir (KWOK_REF_DIR=1, with KWOK_UID_DIR=1 and KWOK_ECHO_LEDGER=1): the engine's reference directory
+	// (kwok_watch.h, DESIGN.md §25) holds what a patch is addressed to; podUID, podRef and nodeName stay
+	// empty: tickApply addresses every body with the reference the tick hands back, setupCNI asks
+	// kwok_refs_lookup, the typed paths name their pods with kwok_refs_bind (bindBatch)
+	refDir      bool
+	batchRefs   map[types.UID]types.NamespacedName // refDir: the typed batch's names by uid (bindBatch)
 	gpuCodec    bool // pod documents decoded on the GPU (kwok_ingest_pods_json); KWOK_GPU_CODEC=0: the host codec
 	podDocsHost int  // pod documents the GPU codec left to the host codec (logged)
 	nodeDocsHost int // node documents the GPU codec left to the host codec (logged)
@@ -288,8 +294,21 @@ func newGPUController(conf Config, interval time.Duration) (*GPUController, erro
 		}
 		ledger = eng
 	}
+	refDir := os.Getenv("KWOK_REF_DIR") == "1"
+	if refDir {
+		if !byUID || ledger == nil {
+			codec.close()
+			eng.close()
+			return nil, fmt.Errorf("KWOK_REF_DIR=1 needs KWOK_UID_DIR=1 and KWOK_ECHO_LEDGER=1")
+		}
+		if err := eng.refsEnable(); err != nil {
+			codec.close()
+			eng.close()
+			return nil, err
+		}
+	}
 	return &GPUController{
-		byUID: byUID,
+		byUID: byUID, refDir: refDir, batchRefs: map[types.UID]types.NamespacedName{},
 		conf: conf, eng: eng, codec: codec, interval: interval, finalizer: finalizerPatch(),
 		nodeName: map[int32]string{}, nodeHandle: map[string]int32{}, podByUID: map[types.UID]int32{},
 		podUID: map[int32]types.UID{},
@@ -397,14 +416,26 @@ func (c *GPUController) listInto(ctx context.Context, nodes bool, opt metav1.Lis
 			if ss[k] != C.KWOK_OK {
 				continue // outside the engine's domain (DESIGN.md §2)
 			}
+			if c.refDir && !nodes && frames[i].flags&(C.KWOK_FRAME_ESC_NAME|C.KWOK_FRAME_ESC_NS) == 0 {
+				continue // (only an item whose name holds an escape is looked at: its decoded text is bound below)
+			}
 			f := &frames[i]
 			name, err := text(staged, f.name, f.flags&C.KWOK_FRAME_ESC_NAME != 0)
 			if err != nil {
 				return "", err
 			}
 			if nodes {
-				c.nodeName[out[k]] = name
-				c.nodeHandle[name] = out[k]
+				c.putNode(out[k], name)
+				continue
+			}
+			if c.refDir { // an escaped name: the device stored none, the decoded text is bound
+				ns, err := text(staged, f.namespace_, f.flags&C.KWOK_FRAME_ESC_NS != 0)
+				if err != nil {
+					return "", err
+				}
+				if _, err := c.eng.refsBind([]int32{out[k]}, []string{ns}, []string{name}); err != nil {
+					return "", err
+				}
 				continue
 			}
 			ns, err := text(staged, f.namespace_, f.flags&C.KWOK_FRAME_ESC_NS != 0)
@@ -629,14 +660,21 @@ func (c *GPUController) tickApply(ctx context.Context, tasks *parallelTasks, now
 	nodesAPI := c.conf.ClientSet.CoreV1().Nodes()
 	var gone []int32
 	n := 0
-	err := c.eng.tick(now, func(kind int, h int32, body []byte) {
+	err := c.eng.tick(now, func(kind int, h int32, body []byte, r *objRef) {
 		if kind == kindHeartbeat && !heartbeats {
+			return
+		}
+		if r != nil && r.status != C.KWOK_OK { // refDir: no name stored, the body cannot be addressed
+			logger.Warn("No reference for an engine body", fmt.Errorf("kwok status %d", r.status))
 			return
 		}
 		n++
 		switch kind {
 		case kindHeartbeat, kindNodeInit: // configureHeartbeatNode / configureNode bodies
 			name := c.nodeName[h]
+			if r != nil {
+				name = r.name
+			}
 			tasks.Add(func() {
 				n, err := nodesAPI.PatchStatus(ctx, name, body)
 				if err != nil {
@@ -647,6 +685,9 @@ func (c *GPUController) tickApply(ctx context.Context, tasks *parallelTasks, now
 			})
 		case kindPodPatch: // LockPod (pod_controller.go:205-231)
 			ref := c.podRef[h]
+			if r != nil {
+				ref = types.NamespacedName{Namespace: r.namespace, Name: r.name}
+			}
 			tasks.Add(func() {
 				p, err := c.conf.ClientSet.CoreV1().Pods(ref.Namespace).Patch(ctx, ref.Name,
 					types.StrategicMergePatchType, body, metav1.PatchOptions{}, "status")
@@ -664,11 +705,14 @@ func (c *GPUController) tickApply(ctx context.Context, tasks *parallelTasks, now
 				}
 			})
 		case kindDelete, kindDeleteFin: // DeletePod (pod_controller.go:155-183); the engine freed the handle
-			ref, fin := c.podRef[h], kind == kindDeleteFin
+			ref, fin, uid := c.podRef[h], kind == kindDeleteFin, c.podUID[h]
+			if r != nil {
+				ref, uid = types.NamespacedName{Namespace: r.namespace, Name: r.name}, types.UID(r.uid)
+			}
 			gone = append(gone, h)
 			// the pod's noted echoes go here, before the task: the echo its finalizer
 			// patch notes (whenever the task runs) is then dropped, not re-ingested
-			c.echo.forget(c.podUID[h])
+			c.echo.forget(uid)
 			tasks.Add(func() {
 				pods := c.conf.ClientSet.CoreV1().Pods(ref.Namespace)
 				if fin { // only pods with finalizers (len(pod.Finalizers) != 0, :161)
@@ -708,8 +752,20 @@ func (c *GPUController) setupCNI(ctx context.Context, tasks *parallelTasks) erro
 	}
 	logger := log.FromContext(ctx)
 	ips := make([]uint32, len(hs))
+	var named []objRef
+	if c.refDir { // the pods that wait for an address, by the names the device holds
+		if named, err = c.eng.refsLookup(C.KWOK_KIND_PODS, hs, 0); err != nil {
+			return err
+		}
+	}
 	for i, h := range hs {
 		i, uid, ref := i, c.podUID[h], c.podRef[h]
+		if c.refDir {
+			if named[i].status != C.KWOK_OK {
+				continue
+			}
+			uid, ref = types.UID(named[i].uid), types.NamespacedName{Namespace: named[i].namespace, Name: named[i].name}
+		}
 		tasks.Add(func() {
 			got, err := cni.Setup(ctx, string(uid), ref.Name, ref.Namespace)
 			if err != nil {
@@ -768,11 +824,30 @@ func (c *GPUController) flushNodes(ctx context.Context, b objBatch) error {
 			delete(c.nodeName, hs[i])
 			delete(c.nodeHandle, name)
 		} else {
-			c.nodeName[hs[i]] = name
-			c.nodeHandle[name] = hs[i]
+			c.putNode(hs[i], name)
 		}
 	}
 	return nil
+}
+
+// putNode: a node the engine created or updated - its handle by name and, without the reference directory,
+// its name by handle
+func (c *GPUController) putNode(h int32, name string) {
+	if !c.refDir {
+		c.nodeName[h] = name
+	}
+	c.nodeHandle[name] = h
+}
+
+// putPod: a pod the engine created or updated - its uid and name by handle (refDir: the device holds them;
+// the typed batch's names are kept by uid for bindBatch)
+func (c *GPUController) putPod(h int32, uid types.UID, ref types.NamespacedName) {
+	if c.refDir {
+		c.batchRefs[uid] = ref
+		return
+	}
+	c.podUID[h] = uid
+	c.podRef[h] = ref
 }
 
 // flushNodesHost: flushNodes with the host codec (kwok_decode_nodes)
@@ -805,8 +880,7 @@ func (c *GPUController) flushNodesHost(ctx context.Context, b objBatch) error {
 			delete(c.nodeName, hs[i])
 			delete(c.nodeHandle, names[i])
 		} else {
-			c.nodeName[hs[i]] = names[i]
-			c.nodeHandle[names[i]] = hs[i]
+			c.putNode(hs[i], names[i])
 		}
 	}
 	return nil
@@ -905,8 +979,7 @@ func (c *GPUController) flushPods(ctx context.Context, tasks *parallelTasks, b o
 				delete(c.podRef, out[k])
 			} else {
 				c.podByUID[uid] = out[k]
-				c.podUID[out[k]] = uid
-				c.podRef[out[k]] = b.refs[i]
+				c.putPod(out[k], uid, b.refs[i])
 			}
 		}
 		return nil
@@ -964,7 +1037,19 @@ func (c *GPUController) bindBatch() error {
 			hs, us = append(hs, h), append(us, u)
 		}
 	}
-	_, err := c.eng.uidBind(hs, us)
+	if _, err := c.eng.uidBind(hs, us); err != nil || !c.refDir {
+		return err
+	}
+	// refDir: ... and named (a typed event carries neither its uid nor its name to the device)
+	hs = hs[:0]
+	nss, names := make([]string, 0, len(c.batchRefs)), make([]string, 0, len(c.batchRefs))
+	for u, ref := range c.batchRefs {
+		if h, ok := c.podByUID[u]; ok && len(ref.Name) > 0 && len(ref.Name) <= C.KWOK_REF_NAME_MAX && len(ref.Namespace) <= C.KWOK_REF_NS_MAX {
+			hs, nss, names = append(hs, h), append(nss, ref.Namespace), append(names, ref.Name)
+		}
+	}
+	c.batchRefs = map[types.UID]types.NamespacedName{}
+	_, err := c.eng.refsBind(hs, nss, names)
 	return err
 }
 
@@ -1042,8 +1127,7 @@ func (c *GPUController) flushPodsHost(ctx context.Context, tasks *parallelTasks,
 				delete(c.podRef, hs[k])
 			} else {
 				c.podByUID[uid] = hs[k]
-				c.podUID[hs[k]] = uid
-				c.podRef[hs[k]] = r.ref
+				c.putPod(hs[k], uid, r.ref)
 			}
 		}
 		return nil

@@ -128,6 +128,17 @@ ECHO = 2        # KWOK_ECHO: a frame dropped as the echo of one of the engine's 
 ECHO_NOTE, ECHO_FORGET = 0, 1  # kwok_echo_update ops
 ECHO_STATS = ("notes", "forgets", "evictions", "matched", "dropped", "kept_matched", "rebuilds", "live_uids",
               "table_entries")  # KWOK_ECHO_STAT_* order
+REF_NS_MAX, REF_NAME_MAX, REF_STRIDE = 63, 253, 320  # KWOK_REF_*: the reference directory's limits and pod record stride
+REF_NONE = 3        # KWOK_REF_NONE: kwok_ref.status of a live pod with no name stored
+REFS_ANY_SLOT = 1   # KWOK_REFS_ANY_SLOT: kwok_refs_lookup answers what the slot last stored, live or not
+REFS_HEARTBEAT, REFS_NODE_INIT, REFS_POD_PATCH, REFS_DELETE = range(4)  # KWOK_REFS_*: the tick's output lists
+REFS_STATS = ("binds", "notes", "unnamed", "reads", "not_found", "bytes")  # KWOK_REFS_STAT_* order
+
+
+class Ref(C.Structure):
+    """kwok_ref: one reference; its bytes are namespace, name, uid at blob + off"""
+    _fields_ = [("off", C.c_uint64), ("ns_len", C.c_uint8), ("name_len", C.c_uint8), ("uid_len", C.c_uint8),
+                ("status", C.c_int8), ("reserved0", C.c_uint32)]
 
 
 class ListInfo(C.Structure):
@@ -196,6 +207,7 @@ POD_REC_DTYPE = _np_dtype(PodRec)
 POD_REC12_DTYPE = _np_dtype(PodRec12)
 WATCH_FRAME_DTYPE = _np_dtype(WatchFrame)
 LIST_INFO_DTYPE = _np_dtype(ListInfo)
+REF_DTYPE = _np_dtype(Ref)
 
 
 def ip4(s: str) -> int:

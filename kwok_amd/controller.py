@@ -294,6 +294,7 @@ class Stats:
     resync_skipped: int = 0     # ... sessions closed without a sweep (a bad page, frame or record: a partial picture)
     bodies: int = 0
     echo_notes_refused: int = 0  # echo_ledger: notes the device ledger refused (a uid / version outside its domain)
+    refs_missing: int = 0       # ref_directory: bodies not sent, their object has no name stored (never with typed / framed feeds)
     rejected: list = field(default_factory=list)
 
 
@@ -310,7 +311,7 @@ class Controller:
                     max_pod_specs=4096)
 
     def __init__(self, conf: Config, backend=None, codec_threads=1, suppress_echoes=True, geometry=None,
-                 gpu_codec=True, uid_directory=False, echo_ledger=False):
+                 gpu_codec=True, uid_directory=False, echo_ledger=False, ref_directory=False):
         self.conf = conf
         # uid_directory: the engine's pod uid directory (kwok_watch.h) resolves metadata.uid -> handle on
         # the device; pod_by_uid stays empty (a uid the directory cannot key - empty, escaped in the
@@ -344,6 +345,18 @@ class Controller:
             if not hasattr(self.eng, "echo_enable"):
                 raise ValueError("echo_ledger needs the engine backend (kwok_echo_enable)")
             self.eng.echo_enable()
+        # ref_directory: the engine's reference directory (kwok_watch.h) holds what a patch is addressed to -
+        # a pod's namespace, name and uid, a node's name - and hands it back in the order of the tick's lists:
+        # pod_ref, pod_uid and node_name stay empty (node_handle and node_uid, the typed pod events' and the
+        # ledger's, stay)
+        self.refs = bool(ref_directory)
+        if self.refs:
+            if not (uid_directory and echo_ledger):
+                raise ValueError("ref_directory needs uid_directory=True and echo_ledger=True")
+            if not hasattr(self.eng, "refs_enable"):
+                raise ValueError("ref_directory needs the engine backend (kwok_refs_enable)")
+            self.eng.refs_enable()
+        self.hb_refs = []     # ref_directory: the heartbeat list's references of epoch hb_epoch
         self.codec = Codec(manage_all_nodes=conf.manage_all_nodes,
                            manage_nodes_with_annotation_selector=conf.manage_nodes_with_annotation_selector,
                            manage_nodes_with_label_selector=conf.manage_nodes_with_label_selector,
@@ -546,12 +559,9 @@ class Controller:
             if st[k] != abi.OK:
                 continue
             if recs[k]["op"] == abi.OP_DELETE:
-                self.node_name.pop(int(hs[k]), None)
-                self.node_handle.pop(names[k], None)
-                self.node_uid.pop(int(hs[k]), None)
+                self._node_pop(int(hs[k]), names[k])
             else:
-                self.node_name[int(hs[k])] = names[k]
-                self.node_handle[names[k]] = int(hs[k])
+                self._node_put(int(hs[k]), names[k])
 
     def _flush_nodes_gpu(self, ws, docs):
         """gpu_controller.go flushNodes on the device codec: the documents straight to
@@ -569,13 +579,27 @@ class Controller:
                     self.stats.rejected.append(("node", name, int(st[k])))
                 continue
             if w.deleted:
-                self.node_name.pop(int(hs[k]), None)
-                self.node_handle.pop(name, None)
-                self.node_uid.pop(int(hs[k]), None)
+                self._node_pop(int(hs[k]), name)
             else:
-                self.node_name[int(hs[k])] = name
-                self.node_handle[name] = int(hs[k])
-                self.node_uid[int(hs[k])] = w.uid
+                self._node_put(int(hs[k]), name, w.uid)
+
+    def _node_put(self, h, name, uid=None):
+        """a node the engine created or updated: its handle by name (and, ref_directory off, its name by handle)"""
+        if not self.refs:
+            self.node_name[h] = name
+        self.node_handle[name] = h
+        if uid is not None:
+            self.node_uid[h] = uid
+
+    def _node_pop(self, h, name):
+        self.node_name.pop(h, None)
+        self.node_handle.pop(name, None)
+        self.node_uid.pop(h, None)
+
+    def _pod_put(self, h, uid, ref):
+        if not self.refs:  # (ref_directory: the device holds them)
+            self.pod_uid[h] = uid
+            self.pod_ref[h] = ref
 
     def _spec_id(self, b, d):
         spec = (tuple((b.text(c.name), b.text(c.image)) for c in d.containers[:d.n_containers]),
@@ -595,7 +619,7 @@ class Controller:
         hs = self.eng.uid_lookup(us) if us else []
         return {u: int(h) for u, h in zip(us, hs) if h >= 0}
 
-    def _uid_bind(self, by_uid, uids):
+    def _uid_bind(self, by_uid, uids, names=None):
         """uid_directory: the pods a typed batch created (or touched) are bound on the device, so that
         raw bytes and typed events of one pod can be mixed"""
         if not self.uid_dir:
@@ -603,6 +627,12 @@ class Controller:
         us = [u for u in dict.fromkeys(uids) if u in by_uid and 0 < len(u.encode()) <= abi.UID_MAX]
         if us:
             self.eng.uid_bind([by_uid[u] for u in us], us)
+        if self.refs and names is not None:  # ... and named (a typed event carries neither to the device)
+            last = {u: r for u, r in zip(uids, names) if u in by_uid}
+            ok = [(by_uid[u], ns.encode(), nm.encode()) for u, (ns, nm) in last.items()]
+            ok = [x for x in ok if 0 < len(x[2]) <= abi.REF_NAME_MAX and len(x[1]) <= abi.REF_NS_MAX]
+            if ok:
+                self.eng.refs_bind([x[0] for x in ok], [x[1] for x in ok], [x[2] for x in ok])
 
     def _flush_pods(self, batch):
         """gpu_controller.go flushPods: decode, then ingest in runs (ingest_pod_runs).
@@ -644,7 +674,7 @@ class Controller:
         refs = [(b.text(b.pods[i].namespace_), b.text(b.pods[i].name)) for i in idx]
         by_uid = self._uid_map(uids)
         hs, st, runs = ingest_pod_runs(self.eng, by_uid, recs, uids, deleted, bytes(b.buf))
-        self._uid_bind(by_uid, uids)
+        self._uid_bind(by_uid, uids, refs)
         self.stats.pod_records += int((st != NOT_SENT).sum())
         self.stats.pod_runs += runs
         for k in range(len(recs)):
@@ -655,8 +685,7 @@ class Controller:
                 self.pod_uid.pop(h, None)
                 self.pod_ref.pop(h, None)
             else:
-                self.pod_uid[h] = uids[k]
-                self.pod_ref[h] = refs[k]
+                self._pod_put(h, uids[k], refs[k])
 
     def _flush_pods_gpu(self, ws, docs):
         """gpu_controller.go flushPodsJSON: the documents straight to
@@ -665,7 +694,8 @@ class Controller:
         deleted = [w.deleted for w in ws]
         by_uid = self._uid_map(uids)
         hs, st, runs, n_host = ingest_doc_runs(self.eng, self.codec, by_uid, docs, uids, deleted)
-        self._uid_bind(by_uid, uids)
+        self._uid_bind(by_uid, uids, [(_meta(w.obj).get("namespace", ""), _meta(w.obj).get("name", "")) for w in ws]
+                       if self.refs else None)
         self.stats.pod_records += int((st != NOT_SENT).sum())
         self.stats.pod_runs += runs
         self.stats.pod_docs_host += n_host
@@ -683,9 +713,7 @@ class Controller:
                     self.pod_uid.pop(int(hs[k]), None)
                     self.pod_ref.pop(int(hs[k]), None)
             else:
-                h = int(hs[k])
-                self.pod_uid[h] = w.uid
-                self.pod_ref[h] = (md.get("namespace", ""), md.get("name", ""))
+                self._pod_put(int(hs[k]), w.uid, (md.get("namespace", ""), md.get("name", "")))
 
     def _flush_watch(self, nodes):
         """the raw bytes of one kind's watch: framed on the GPU, then _ingest_frames:
@@ -745,10 +773,23 @@ class Controller:
             return
         hs, _rel, nd = self.eng.resync_sweep(kind)
         if nodes:
+            # (ref_directory: a swept node's entry may be gone with its name; node_handle still names it)
+            by_handle = {v: k for k, v in self.node_handle.items()} if self.refs and len(hs) else self.node_name
             for h in hs.tolist():
-                self.node_handle.pop(self.node_name.pop(h, None), None)
+                self.node_handle.pop(by_handle.pop(h, None), None)
                 self._forget(self.node_uid.pop(h, None))
             self.stats.resync_swept_nodes += len(hs)
+            self._send_echo()
+            return
+        if self.refs:  # the swept pods' slots keep their bytes until the next pod ingest
+            cni = self.conf.enable_cni and self.conf.cni
+            pods = self.eng.ref_items(*self.eng.refs_lookup(abi.KIND_PODS, hs, abi.REFS_ANY_SLOT)) if len(hs) else []
+            on = self.eng.ref_items(*self.eng.refs_lookup(abi.KIND_NODES, nd)) if cni and len(hs) else []
+            for k, (status, ns, name, uid) in enumerate(pods):
+                if cni and status == abi.OK and self.has(on[k][2].decode()):
+                    self.conf.cni.remove(uid.decode(), name.decode(), ns.decode())
+                self._forget(uid.decode())
+            self.stats.resync_swept_pods += len(hs)
             self._send_echo()
             return
         for h, n in zip(hs.tolist(), nd.tolist()):
@@ -823,13 +864,9 @@ class Controller:
                         sess["dirty"] = True
                     continue
                 if deleted[k]:
-                    self.node_name.pop(int(hs[k]), None)
-                    self.node_handle.pop(name(i), None)
-                    self.node_uid.pop(int(hs[k]), None)
+                    self._node_pop(int(hs[k]), name(i))
                 else:
-                    self.node_name[int(hs[k])] = name(i)
-                    self.node_handle[name(i)] = int(hs[k])
-                    self.node_uid[int(hs[k])] = uids[k]
+                    self._node_put(int(hs[k]), name(i), uids[k])
             return
         n_host = [0]
 
@@ -864,9 +901,7 @@ class Controller:
                     self.pod_uid.pop(int(hs[k]), None)
                     self.pod_ref.pop(int(hs[k]), None)
             else:
-                h = int(hs[k])
-                self.pod_uid[h] = uids[k]
-                self.pod_ref[h] = (ns(i), name(i))
+                self._pod_put(int(hs[k]), uids[k], (ns(i), name(i)))
 
     def _ingest_frames_ledger(self, nodes, stream, frames, sid, sess, text, name, ns):
         """_ingest_frames with the echo ledger: ALL frames of the batch in one call per kind, the echoes
@@ -929,17 +964,33 @@ class Controller:
                     if sess is not None and st[i] in partial:
                         sess["dirty"] = True
                 elif ty[i] == abi.WATCH_DELETED:
-                    self.node_name.pop(h, None)
-                    self.node_handle.pop(name(i), None)
-                    self.node_uid.pop(h, None)
-                elif h not in self.node_name:  # a create (a known node keeps its name and uid)
-                    self.node_name[h] = name(i)
-                    self.node_handle[name(i)] = h
-                    self.node_uid[h] = uid_of(i)
+                    self._node_pop(h, name(i))
+                elif h not in (self.node_uid if self.refs else self.node_name):  # a create (a known node keeps its name and uid)
+                    self._node_put(h, name(i), uid_of(i))
             return
         self.stats.pod_records += int((st[keep] != NOT_SENT).sum())
         self.stats.pod_runs += runs
         self.stats.pod_docs_host += nh
+        if self.refs:
+            # the device stored every create's namespace and name from its frame: only rejected records, CNI
+            # deletes and creates whose frame holds an escaped name (their decoded text is bound) are looked at
+            sent = np.isin(st[keep], (abi.OK, NOT_SENT))
+            dels = keep[sent & (ty[keep] == abi.WATCH_DELETED)] if self.conf.enable_cni and self.conf.cni else keep[:0]
+            escn = keep[(st[keep] == abi.OK) & (ty[keep] != abi.WATCH_DELETED) &
+                        ((fl[keep] & (abi.FRAME_ESC_NAME | abi.FRAME_ESC_NS)) != 0)]
+            for i in sorted(keep[~sent].tolist() + dels.tolist()):
+                if st[i] not in (abi.OK, NOT_SENT):
+                    self.stats.rejected.append(("pod", name(i), int(st[i])))
+                    if sess is not None and st[i] in partial:
+                        sess["dirty"] = True
+                else:
+                    f = frames[i]
+                    obj = json.loads(stream[int(f["doc_off"]):int(f["doc_off"]) + int(f["doc_len"])])
+                    if self.has((obj.get("spec") or {}).get("nodeName", "")):
+                        self.conf.cni.remove(uid_of(i), name(i), ns(i))
+            if len(escn):
+                self.eng.refs_bind(hs[escn], [ns(i).encode() for i in escn], [name(i).encode() for i in escn])
+            return
         for i in keep.tolist():
             h = int(hs[i])
             if st[i] not in (abi.OK, NOT_SENT):
@@ -964,8 +1015,16 @@ class Controller:
         if not len(hs):
             return
         keep, ips = [], []
-        for h in hs:
-            uid, (ns, name) = self.pod_uid[int(h)], self.pod_ref[int(h)]
+        named = self.eng.ref_items(*self.eng.refs_lookup(abi.KIND_PODS, hs)) if self.refs else None
+        for k, h in enumerate(hs):
+            if named is not None:
+                status, ns, name, uid = named[k]
+                if status != abi.OK:
+                    self.stats.refs_missing += 1
+                    continue
+                uid, ns, name = uid.decode(), ns.decode(), name.decode()
+            else:
+                uid, (ns, name) = self.pod_uid[int(h)], self.pod_ref[int(h)]
             try:
                 got = self.conf.cni.setup(uid, name, ns)
             except Exception:  # a failed Setup leaves the pod unpatched this tick
@@ -995,21 +1054,25 @@ class Controller:
                           p("dl"), p("dlf"), None, 0, 0)
         e._check(e._fn("read_outputs")(e._h, C.byref(out)), "read_outputs")
         self.hb_epoch = res.heartbeat_epoch
+        if self.refs and new_epoch:  # the heartbeat list's references change with the handle list
+            self.hb_refs = self._read_refs(abi.REFS_HEARTBEAT, 0, res.n_heartbeat)
         n = 0
         if res.n_heartbeat and heartbeats:
             body = e.read_arena(out.heartbeat_off, res.heartbeat_len).tobytes()
-            for h in self.hb:
-                self._apply(HEARTBEAT, int(h), body)
+            for k, h in enumerate(self.hb):
+                self._apply(HEARTBEAT, int(h), body, self.hb_refs[k] if self.refs else None)
                 n += 1
-        n += self._apply_patches(NODE_INIT, L["ini"], L["ini_off"], L["ini_len"])
-        n += self._apply_patches(POD_PATCH, L["pp"], L["pp_off"], L["pp_len"])
+        n += self._apply_patches(NODE_INIT, L["ini"], L["ini_off"], L["ini_len"], abi.REFS_NODE_INIT)
+        n += self._apply_patches(POD_PATCH, L["pp"], L["pp_off"], L["pp_len"], abi.REFS_POD_PATCH)
         gone = []
-        for h, f in zip(L["dl"], L["dlf"]):  # Patch(removeFinalizers) if finalizers, then Delete(grace 0)
+        dl_refs = self._read_refs(abi.REFS_DELETE, 0, res.n_delete) if self.refs else None  # (the tick freed them: their bytes stay)
+        for k, (h, f) in enumerate(zip(L["dl"], L["dlf"])):  # Patch(removeFinalizers) if finalizers, then Delete(grace 0)
             # the engine freed the handle: the pod's noted echoes go BEFORE the apply, so
             # that the echo of its finalizer patch (noted by the apply) is dropped
             # (gpu_controller.go forgets in the tick callback, ahead of the task)
-            self._forget(self.pod_uid.get(int(h)))
-            self._apply(DELETE_FIN if f else DELETE, int(h), None)
+            ref = dl_refs[k] if self.refs else None
+            self._forget(ref[3].decode() if ref else self.pod_uid.get(int(h)))
+            self._apply(DELETE_FIN if f else DELETE, int(h), None, ref)
             gone.append(int(h))
             n += 1
         for h in gone:  # the later Deleted watch event finds no handle
@@ -1020,30 +1083,44 @@ class Controller:
         self._send_echo()
         return n
 
-    def _apply_patches(self, kind, hs, offs, lens):
+    REFS_PIECE = 1 << 16  # ref_directory: references read per kwok_read_refs call at most
+
+    def _read_refs(self, which, first, count):
+        """items [first, first + count) of a list of the collected tick: [(status, namespace, name, uid)]"""
+        out = []
+        for lo in range(first, first + count, self.REFS_PIECE):
+            out += self.eng.ref_items(*self.eng.read_refs(which, lo, min(self.REFS_PIECE, first + count - lo)))
+        return out
+
+    def _apply_patches(self, kind, hs, offs, lens, which=None):
         i = n = 0
         ends = offs.astype(np.int64) + lens
         while i < len(hs):
             lo = int(offs[i])
             j = max(i + 1, int(np.searchsorted(ends, lo + READ_CHUNK, side="right")))
             buf = self.eng.read_arena(lo, int(ends[j - 1]) - lo).tobytes()
+            refs = self._read_refs(which, i, j - i) if self.refs else None  # (the piece's references beside its bytes)
             for k in range(i, j):
                 o = int(offs[k]) - lo
-                self._apply(kind, int(hs[k]), buf[o:o + int(lens[k])])
+                self._apply(kind, int(hs[k]), buf[o:o + int(lens[k])], refs[k - i] if refs else None)
                 n += 1
             i = j
         return n
 
-    def _apply(self, kind, h, body):
+    def _apply(self, kind, h, body, ref=None):
+        """ref (ref_directory): the object's (status, namespace, name, uid) from the device, else the maps'"""
         cs = self.conf.client_set
+        if ref is not None and ref[0] != abi.OK:  # no name stored: the body cannot be addressed
+            self.stats.refs_missing += 1
+            return
         if kind in (HEARTBEAT, NODE_INIT):  # configureHeartbeatNode / configureNode bodies
             try:
-                obj = cs.patch_node_status(self.node_name[h], body)
+                obj = cs.patch_node_status(ref[2].decode() if ref else self.node_name[h], body)
             except NotFound:
                 return
             self._note(_meta(obj).get("uid"), _meta(obj).get("resourceVersion"))
         elif kind == POD_PATCH:  # LockPod (pod_controller.go:205-231)
-            ns, name = self.pod_ref[h]
+            ns, name = (ref[1].decode(), ref[2].decode()) if ref else self.pod_ref[h]
             try:
                 obj = cs.patch_pod_status(ns, name, body)
             except NotFound:
@@ -1052,7 +1129,7 @@ class Controller:
             if b'"podIP"' not in body:  # an empty status: its echo re-enters (step 6)
                 self.reenter.append(obj)
         else:  # DeletePod (pod_controller.go:155-183)
-            ns, name = self.pod_ref[h]
+            ns, name = (ref[1].decode(), ref[2].decode()) if ref else self.pod_ref[h]
             if kind == DELETE_FIN:
                 if self.finalizer is None:
                     from .engine import finalizer_patch

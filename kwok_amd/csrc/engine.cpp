@@ -369,6 +369,40 @@ struct kwok_engine {
         EchoLedger ledger() const { return EchoLedger{tab, (uint32_t)(tab_cap - 1), pool, (uint32_t)pool_cap, ctr}; }
     } echo;
 
+    // ---- the pod and node reference directory (refs.hip, kwok_watch.h): namespace and name per pod
+    // slot, the per-call buffers of bind / lookup / read ----
+    struct Refs {
+        struct Bytes {
+            uint8_t b[KWOK_REF_STRIDE];
+        };
+        bool on = false;
+        Bytes* pod_ref = nullptr;         // [PLa] re-laid out with the pod arrays (grow_pods)
+        uint16_t* pod_ref_len = nullptr;  // [PLa]
+        RefCounters* ctr = nullptr;       // device
+        RefCounters* ctr_h = nullptr;     // pinned
+        // the stale guard: per kind (KWOK_KIND_*), bumped by every call that can create an object of it
+        uint64_t gen[2] = {0, 0};
+        // lookup / read: handles, sizes, offsets, slots, references, the scan's storage, the blob
+        size_t qcap = 0, tmp_bytes = 0, blob_cap = 0;
+        int32_t* q_h = nullptr;
+        uint64_t *q_len = nullptr, *q_off = nullptr;
+        uint32_t* q_slot = nullptr;
+        kwok_ref* q_refs = nullptr;
+        void* q_tmp = nullptr;
+        uint8_t* q_blob = nullptr;
+        // bind: the spans (namespaces, then names) and the caller's arena
+        size_t bcap = 0, acap = 0;
+        uint64_t* b_off = nullptr;
+        uint32_t* b_len = nullptr;
+        uint8_t* b_arena = nullptr;
+        // the by-uid batch whose records the ingest is applying (null: an entry that carries no name)
+        const RefNote* note = nullptr;
+    } refs;
+    RefDir ref_dir() const {
+        return RefDir{reinterpret_cast<uint8_t*>(refs.pod_ref), refs.pod_ref_len, reinterpret_cast<const uint8_t*>(uid.pod_uid),
+                      uid.pod_uid_len, refs.ctr};
+    }
+
     // ---- the pod codec on the GPU (json.hip): per-document buffers, the codec's
     // selectors, the spec table (kwok_spec_key -> spec id) ----
     struct Json {
@@ -482,6 +516,7 @@ struct kwok_engine {
         uint64_t now = 0, target = 0;
         uint32_t tag = 0;
         uint32_t epoch = 0;         // heartbeat_epoch of the tick
+        uint64_t ref_gen[2] = {0, 0};  // the reference directory's counters at the tick's submit (kwok_read_refs)
         int rc = 0;
         std::string err;
         kwok_tick_result res{};
@@ -980,6 +1015,8 @@ int grow_pods(kwok_engine* e, uint32_t new_cp) {
     // the uid directory's per-slot uids move with their pods (handles are stable; the table is rebuilt
     // to the new size before its next use, uid_ensure)
     if (e->uid.on && ((rc = relayout(e->uid.pod_uid)) || (rc = relayout(e->uid.pod_uid_len)))) return rc;
+    // ... and the reference directory's namespaces and names
+    if (e->refs.on && ((rc = relayout(e->refs.pod_ref)) || (rc = relayout(e->refs.pod_ref_len)))) return rc;
     for (auto& T : e->slots) {
         if (!T.alloc) continue;
         if ((rc = resize(T.pp_pods, true)) || (rc = resize(T.pp_off, true)) || (rc = resize(T.pp_len, true)) ||
@@ -1323,6 +1360,14 @@ void kwok_engine_destroy(kwok_engine* e) {
             if (p) (void)hipFree(p);
         if (U.ctr_h) (void)hipHostFree(U.ctr_h);
         if (U.run_h) (void)hipHostFree(U.run_h);
+    }
+    {
+        auto& R = e->refs;
+        void* rp[] = {R.pod_ref, R.pod_ref_len, R.ctr, R.q_h, R.q_len, R.q_off, R.q_slot, R.q_refs, R.q_tmp, R.q_blob, R.b_off,
+                      R.b_len, R.b_arena};
+        for (void* p : rp)
+            if (p) (void)hipFree(p);
+        if (R.ctr_h) (void)hipHostFree(R.ctr_h);
     }
     {
         auto& E = e->echo;
@@ -1886,6 +1931,7 @@ int ingest_nodes_impl(kwok_engine* e, const kwok_node_event* ev, size_t n, const
                       int32_t* out_handles, int32_t* out_status, const NodeJsonCtx* nj) {
     const auto t0 = clk::now();
     int rc = 0;
+    if (e->refs.on && n) e->refs.gen[KWOK_KIND_NODES]++;  // (kwok_read_refs' stale guard: the batch may create nodes)
     auto& G = e->ing;
     hipStream_t st = e->st;
     // the empty-status blob (kwok's own fleets create Nodes with an empty status)
@@ -2086,6 +2132,7 @@ int ingest_pods_impl(kwok_engine* e, const void* recs, int packed, size_t n, con
     e->quiet = 0;
     e->sum_valid = false;
     if (!n) return tick_now >= 0 ? tick_submit_impl(e, tick_now) : 0;
+    if (e->refs.on) e->refs.gen[KWOK_KIND_PODS]++;  // (kwok_read_refs' stale guard: the batch may create pods)
     e->pod_records_since_tick += n;
     const auto t0 = clk::now();
     int rc = ingest_reserve(e, n, e->ing.arena_src ? 0 : arena_len);  // (a framed batch: its strings are resident)
@@ -2258,6 +2305,15 @@ int ingest_pods_impl(kwok_engine* e, const void* recs, int packed, size_t n, con
         }
         launch_uid_note(e->S, I, e->uid.dir(), N, st);
         if (pe[1]) (void)hipEventRecord(pe[1], st);
+        if (e->refs.on) {  // the reference directory: the creates' namespaces and names, or none
+            RefNote RN{};
+            if (e->refs.note) {
+                const size_t lo = lo_of(k);
+                RN = *e->refs.note;
+                RN.frame_idx += lo, RN.cls += lo;
+            }
+            launch_refs_note(e->S, I, e->ref_dir(), RN, st);
+        }
         HIPCHK(e, hipGetLastError());
         return KWOK_OK;
     };
@@ -3700,6 +3756,11 @@ struct NoteSrc {  // the ingest notes the by-uid batch's creates with their uids
     NoteSrc(kwok_engine* e_, const UidNote* n) : e(e_) { e->uid.note = n; }
     ~NoteSrc() { e->uid.note = nullptr; }
 };
+struct RefNoteSrc {  // ... and, with the reference directory, with their frames' namespaces and names
+    kwok_engine* e;
+    RefNoteSrc(kwok_engine* e_, const RefNote* n) : e(e_) { e->refs.note = n; }
+    ~RefNoteSrc() { e->refs.note = nullptr; }
+};
 }  // namespace
 
 int kwok_uid_dir_enable(kwok_engine* e) {
@@ -3924,6 +3985,8 @@ int pods_framed_uid_impl(kwok_engine* e, const kwok_codec* c, uint64_t stream_id
             }
             const UidNote N{Wt.stream, U.uoff + lo, U.ulen + lo, U.hash + lo, U.cls + lo};
             NoteSrc note(e, &N);
+            const RefNote RN{Wt.stream, Wt.len, Wt.frames, B.n_frames, U.fidx + lo, U.cls + lo};
+            RefNoteSrc ref_note(e, &RN);
             ArenaSrc src(e, Wt.stream);
             rc = ingest_pods_impl(e, G.d_ev, 0, m, nullptr, Wt.len, nullptr, nullptr, nullptr, nullptr, true);
             for (size_t q = 0; q + 1 < U.note_ev.size(); q += 2) {  // (the batch is synchronised, or failed)
@@ -4367,6 +4430,237 @@ int kwok_echo_stats(kwok_engine* e, uint64_t out[KWOK_ECHO_STAT_COUNT]) {
     out[KWOK_ECHO_STAT_REBUILDS] = E.rebuilds;
     out[KWOK_ECHO_STAT_LIVE_UIDS] = E.ctr_h->live;
     out[KWOK_ECHO_STAT_TABLE_ENTRIES] = E.ctr_h->used;
+    return KWOK_OK;
+}
+
+// ---- the pod and node reference directory (kwok_watch.h, refs.hip) -------------------
+namespace {
+int refs_read_counters(kwok_engine* e) {
+    auto& R = e->refs;
+    HIPCHK(e, hipMemcpyAsync(R.ctr_h, R.ctr, sizeof(RefCounters), hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    return KWOK_OK;
+}
+// items [first, first + n) of the device handle list `handles`: sizes, scan, gather, then refs[] and the blob to
+// the caller (on the engine stream: behind every ingest and every submitted tick)
+int refs_query(kwok_engine* e, const char* who, const int32_t* handles, size_t first, size_t n, bool pods, bool any_slot,
+               kwok_ref* refs, char* blob, size_t blob_cap, size_t* blob_used) {
+    auto& R = e->refs;
+    hipStream_t st = e->st;
+    if (!n) return KWOK_OK;
+    int rc = 0;
+    if (n > R.qcap) {
+        dfree(R.q_len), dfree(R.q_off), dfree(R.q_slot), dfree(R.q_refs);
+        R.qcap = 0;
+        const size_t cap = std::max<size_t>(n + n / 4, 4096);
+        if ((rc = dalloc(e, &R.q_len, cap)) || (rc = dalloc(e, &R.q_off, cap)) || (rc = dalloc(e, &R.q_slot, cap)) ||
+            (rc = dalloc(e, &R.q_refs, cap)))
+            return rc;
+        R.qcap = cap;
+    }
+    const size_t tmp = refs_scan_bytes((uint32_t)n);
+    if (tmp > R.tmp_bytes) {
+        if (R.q_tmp) (void)hipFree(R.q_tmp);
+        R.q_tmp = nullptr, R.tmp_bytes = 0;
+        const size_t want = tmp + tmp / 4 + 256;
+        if (hipMalloc(&R.q_tmp, want) != hipSuccess) return e->fail(KWOK_ENOMEM, "%s: scan storage", who);
+        R.tmp_bytes = want;
+    }
+    RefQuery Q{};
+    Q.handles = handles;
+    Q.first = (uint32_t)first, Q.n = (uint32_t)n;
+    Q.pods = pods ? 1u : 0u, Q.any_slot = any_slot ? 1u : 0u;
+    Q.len = R.q_len, Q.off = R.q_off, Q.refs = R.q_refs;
+    // KWOK_INGEST_PROF: device-side stamps around k_refs_size, the scan and k_refs_gather
+    const auto t0 = clk::now();
+    hipEvent_t pev[5] = {};
+    if (e->iprof)
+        for (auto& x : pev) (void)hipEventCreate(&x);
+    struct PevGuard {
+        hipEvent_t* p;
+        ~PevGuard() {
+            for (int k = 0; k < 5; k++)
+                if (p[k]) (void)hipEventDestroy(p[k]);
+        }
+    } pev_guard{pev};
+    if (pev[0]) (void)hipEventRecord(pev[0], st);
+    launch_refs_size(e->S, e->ref_dir(), Q, R.q_slot, st);
+    if (pev[1]) (void)hipEventRecord(pev[1], st);
+    HIPCHK(e, hipGetLastError());
+    if (launch_refs_scan(Q, R.q_tmp, R.tmp_bytes, st)) return e->fail(KWOK_EDEVICE, "%s: scan", who);
+    if (pev[2]) (void)hipEventRecord(pev[2], st);
+    uint64_t tail[2] = {0, 0};  // the last item's offset and size: the total
+    HIPCHK(e, hipMemcpyAsync(&tail[0], R.q_off + (n - 1), 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipMemcpyAsync(&tail[1], R.q_len + (n - 1), 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    const uint64_t total = tail[0] + tail[1];
+    if (blob_used) *blob_used = (size_t)total;
+    if (total > blob_cap || (total && !blob))
+        return e->fail(KWOK_EINVAL, "%s: blob_cap %zu < %llu", who, blob_cap, (unsigned long long)total);
+    if (total > R.blob_cap) {
+        dfree(R.q_blob);
+        R.blob_cap = 0;
+        const size_t cap = std::max<size_t>(total + total / 4, 1 << 16);
+        if ((rc = dalloc(e, &R.q_blob, cap))) return rc;
+        R.blob_cap = cap;
+    }
+    Q.blob = R.q_blob;
+    if (pev[3]) (void)hipEventRecord(pev[3], st);
+    launch_refs_gather(e->S, e->ref_dir(), Q, R.q_slot, st);
+    if (pev[4]) (void)hipEventRecord(pev[4], st);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(refs, R.q_refs, n * sizeof(kwok_ref), hipMemcpyDeviceToHost, st));
+    if (total) HIPCHK(e, hipMemcpyAsync(blob, R.q_blob, total, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    if (pev[4]) {
+        float ms_size = 0, ms_scan = 0, ms_gather = 0;
+        (void)hipEventElapsedTime(&ms_size, pev[0], pev[1]);
+        (void)hipEventElapsedTime(&ms_scan, pev[1], pev[2]);
+        (void)hipEventElapsedTime(&ms_gather, pev[3], pev[4]);
+        fprintf(stderr, "[kwok refs] %s: %zu %s, %llu blob bytes: k_refs_size %.3f ms, scan %.3f ms, k_refs_gather %.3f ms; "
+                        "the call %.2f ms\n", who, n, pods ? "pods" : "nodes", (unsigned long long)total, ms_size, ms_scan, ms_gather,
+                ms_between(t0, clk::now()));
+    }
+    return KWOK_OK;
+}
+}  // namespace
+
+int kwok_refs_enable(kwok_engine* e) {
+    if (!e) return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    if (e->multi) return e->fail(KWOK_EINVAL, "kwok_refs_enable: single-rank engines only");
+    auto& R = e->refs;
+    if (R.on) return KWOK_OK;
+    int rc = kwok_uid_dir_enable(e);  // (drains; the references ride on its run cuts)
+    if (rc) return rc;
+    if (!R.ctr) {
+        if ((rc = dalloc(e, &R.ctr, 1))) return rc;
+        if (hipHostMalloc((void**)&R.ctr_h, sizeof(RefCounters), hipHostMallocDefault) != hipSuccess)
+            return e->fail(KWOK_ENOMEM, "reference directory staging");
+        memset(R.ctr_h, 0, sizeof(RefCounters));
+    }
+    // (dalloc zeroes: no pod has a name)
+    if (!R.pod_ref && (rc = dalloc(e, &R.pod_ref, e->PLa))) return rc;
+    if (!R.pod_ref_len && (rc = dalloc(e, &R.pod_ref_len, e->PLa))) return rc;
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    R.on = true;
+    return KWOK_OK;
+}
+
+int kwok_refs_bind(kwok_engine* e, const int32_t* handles, const char* arena, const uint64_t* ns_off,
+                   const uint32_t* ns_len, const uint64_t* name_off, const uint32_t* name_len, size_t n, size_t* n_bad) {
+    if (n_bad) *n_bad = 0;
+    if (!e || (n && (!handles || !ns_off || !ns_len || !name_off || !name_len)) || n > 0x0FFFFFF0ull) return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    auto& R = e->refs;
+    if (!R.on) return e->fail(KWOK_EINVAL, "kwok_refs_bind: the reference directory is not enabled");
+    drain(e);  // (a handle is judged against the state after every submitted tick)
+    if (e->poisoned) return poisoned(e);
+    if (!n) return KWOK_OK;
+    R.gen[KWOK_KIND_PODS]++;
+    uint64_t al = 0;  // (the bytes the valid spans name; a span past 2^40 is the caller's error)
+    for (size_t i = 0; i < n; i++) {
+        if (!name_len[i] || name_len[i] > KWOK_REF_NAME_MAX || ns_len[i] > KWOK_REF_NS_MAX) continue;
+        if (name_off[i] < (1ull << 40)) al = std::max<uint64_t>(al, name_off[i] + name_len[i]);
+        if (ns_len[i] && ns_off[i] < (1ull << 40)) al = std::max<uint64_t>(al, ns_off[i] + ns_len[i]);
+    }
+    if (al && !arena) return KWOK_EINVAL;
+    int rc = 0;
+    if (n > R.bcap) {
+        dfree(R.b_off), dfree(R.b_len), dfree(R.q_h);
+        R.bcap = 0;
+        const size_t cap = std::max<size_t>(n + n / 4, 4096);
+        if ((rc = dalloc(e, &R.b_off, 2 * cap)) || (rc = dalloc(e, &R.b_len, 2 * cap)) || (rc = dalloc(e, &R.q_h, cap))) return rc;
+        R.bcap = cap;
+    }
+    if (al + 1 > R.acap) {
+        dfree(R.b_arena);
+        R.acap = 0;
+        const size_t cap = std::max<size_t>(al + al / 4 + 1, 1 << 16);
+        if ((rc = dalloc(e, &R.b_arena, cap))) return rc;
+        R.acap = cap;
+    }
+    hipStream_t st = e->st;
+    HIPCHK(e, hipMemcpyAsync(R.q_h, handles, n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(R.b_off, ns_off, n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(R.b_off + n, name_off, n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(R.b_len, ns_len, n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(R.b_len + n, name_len, n * 4, hipMemcpyHostToDevice, st));
+    if (al) HIPCHK(e, hipMemcpyAsync(R.b_arena, arena, al, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemsetAsync(&R.ctr->bad, 0, sizeof(R.ctr->bad), st));
+    launch_refs_bind(e->S, e->ref_dir(), R.q_h, R.b_arena, al, R.b_off, R.b_len, R.b_off + n, R.b_len + n, (uint32_t)n, st);
+    HIPCHK(e, hipGetLastError());
+    if ((rc = refs_read_counters(e))) return rc;
+    if (n_bad) *n_bad = (size_t)R.ctr_h->bad;
+    return KWOK_OK;
+}
+
+int kwok_refs_lookup(kwok_engine* e, int kind, const int32_t* handles, size_t n, uint32_t flags, kwok_ref* refs,
+                     char* blob, size_t blob_cap, size_t* blob_used) {
+    if (blob_used) *blob_used = 0;
+    if (!e || (n && (!handles || !refs)) || n > 0x0FFFFFF0ull) return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    auto& R = e->refs;
+    if (!R.on) return e->fail(KWOK_EINVAL, "kwok_refs_lookup: the reference directory is not enabled");
+    if (kind != KWOK_KIND_PODS && kind != KWOK_KIND_NODES) return e->fail(KWOK_EINVAL, "kwok_refs_lookup: kind %d", kind);
+    if (flags & ~(uint32_t)KWOK_REFS_ANY_SLOT) return e->fail(KWOK_EINVAL, "kwok_refs_lookup: flags %u", flags);
+    drain(e);
+    if (e->poisoned) return poisoned(e);
+    if (!n) return KWOK_OK;
+    if (n > R.bcap) {  // (q_h is sized with the bind's buffers)
+        dfree(R.b_off), dfree(R.b_len), dfree(R.q_h);
+        R.bcap = 0;
+        const size_t cap = std::max<size_t>(n + n / 4, 4096);
+        int rc = 0;
+        if ((rc = dalloc(e, &R.b_off, 2 * cap)) || (rc = dalloc(e, &R.b_len, 2 * cap)) || (rc = dalloc(e, &R.q_h, cap))) return rc;
+        R.bcap = cap;
+    }
+    HIPCHK(e, hipMemcpyAsync(R.q_h, handles, n * 4, hipMemcpyHostToDevice, e->st));
+    return refs_query(e, "kwok_refs_lookup", R.q_h, 0, n, kind == KWOK_KIND_PODS, (flags & KWOK_REFS_ANY_SLOT) != 0, refs, blob,
+                      blob_cap, blob_used);
+}
+
+int kwok_read_refs(kwok_engine* e, int which, size_t first, size_t count, kwok_ref* refs, char* blob, size_t blob_cap,
+                   size_t* blob_used) {
+    if (blob_used) *blob_used = 0;
+    if (!e || (count && !refs)) return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    auto& R = e->refs;
+    if (!R.on) return e->fail(KWOK_EINVAL, "kwok_read_refs: the reference directory is not enabled");
+    if (which < 0 || which >= KWOK_REFS_LIST_COUNT) return e->fail(KWOK_EINVAL, "kwok_read_refs: list %d", which);
+    if (e->cur < 0) return e->fail(KWOK_EINVAL, "no collected tick (or its slot was reused by a submit)");
+    const kwok_engine::TickSlot& T = e->slots[e->cur];
+    const TickHdr& H = *T.hdr_h;
+    const int kind = which == KWOK_REFS_HEARTBEAT || which == KWOK_REFS_NODE_INIT ? KWOK_KIND_NODES : KWOK_KIND_PODS;
+    // the stale guard: an ingest since the tick's submit may have created into a slot the list names
+    if (R.gen[kind] != T.ref_gen[kind])
+        return e->fail(KWOK_EINVAL, "kwok_read_refs: stale: %s were ingested or bound since the collected tick's submit",
+                       kind == KWOK_KIND_PODS ? "pods" : "nodes");
+    const int32_t* list = which == KWOK_REFS_HEARTBEAT ? T.hb_nodes : which == KWOK_REFS_NODE_INIT ? T.init_nodes :
+                          which == KWOK_REFS_POD_PATCH ? T.pp_pods : T.del_pods;
+    const size_t total = which == KWOK_REFS_HEARTBEAT ? H.n_hb : which == KWOK_REFS_NODE_INIT ? H.n_init :
+                         which == KWOK_REFS_POD_PATCH ? H.n_pp : H.n_del;
+    if (first > total || count > total - first)
+        return e->fail(KWOK_EINVAL, "kwok_read_refs: range [%zu, +%zu) outside the list's %zu items", first, count, total);
+    // (the tick named these objects; it, or a tick queued behind it, may have freed them since: their bytes stay)
+    return refs_query(e, "kwok_read_refs", list, first, count, kind == KWOK_KIND_PODS, true, refs, blob, blob_cap, blob_used);
+}
+
+int kwok_refs_stats(kwok_engine* e, uint64_t out[KWOK_REFS_STAT_COUNT]) {
+    if (!e || !out) return KWOK_EINVAL;
+    auto& R = e->refs;
+    for (int k = 0; k < KWOK_REFS_STAT_COUNT; k++) out[k] = 0;
+    if (!R.ctr) return KWOK_OK;
+    if (!e->poisoned)
+        if (int rc = refs_read_counters(e)) return rc;
+    out[KWOK_REFS_STAT_BINDS] = R.ctr_h->binds;
+    out[KWOK_REFS_STAT_NOTES] = R.ctr_h->notes;
+    out[KWOK_REFS_STAT_UNNAMED] = R.ctr_h->unnamed;
+    out[KWOK_REFS_STAT_READS] = R.ctr_h->reads;
+    out[KWOK_REFS_STAT_NOT_FOUND] = R.ctr_h->not_found;
+    out[KWOK_REFS_STAT_BYTES] = (uint64_t)e->PLa * (KWOK_REF_STRIDE + sizeof(uint16_t)) + sizeof(RefCounters) +
+                                (uint64_t)R.qcap * (8 + 8 + 4 + sizeof(kwok_ref)) + R.tmp_bytes + R.blob_cap +
+                                (uint64_t)R.bcap * (2 * 8 + 2 * 4 + 4) + R.acap;
     return KWOK_OK;
 }
 
@@ -5128,6 +5422,7 @@ int tick_submit_impl(kwok_engine* e, int64_t now_unix) {
     if (k == e->cur) e->cur = -1;  // its outputs are overwritten
     T.now = (uint64_t)now_unix;
     T.epoch = e->hb_epoch;
+    T.ref_gen[0] = e->refs.gen[0], T.ref_gen[1] = e->refs.gen[1];
     T.emit_queued = e->emit_hint;
     e->emit_hint = false;
     // multi rank: every rank's pods hold the addresses the global pool gave them

@@ -455,4 +455,50 @@ void launch_uid_lookup(const DevState& S, const UidDir& D, const uint8_t* arena,
                        const uint32_t* len, uint32_t n, int32_t* out, hipStream_t st);
 void launch_uid_rebuild(const DevState& S, const UidDir& D, hipStream_t st);
 
+// ---- the pod and node reference directory (refs.hip, kwok_watch.h): what a patch is addressed to ----
+// (kept out of DevState, beside UidDir: no kernel outside refs.hip sees it)
+struct RefCounters {  // device memory, read back by the host
+    unsigned long long binds, notes, unnamed, reads, not_found;
+    unsigned long long bad;  // kwok_refs_bind: records that stored nothing (reset per call)
+};
+struct RefDir {
+    uint8_t* pod_ref;            // [PLa][KWOK_REF_STRIDE] namespace then name from the record's first byte
+    uint16_t* pod_ref_len;       // [PLa] ns_len | name_len << 8; 0: no name stored
+    const uint8_t* pod_uid;      // the uid directory's per-slot uids (read only)
+    const uint8_t* pod_uid_len;
+    RefCounters* ctr;
+};
+// what k_refs_note needs of a by-uid batch, at the chunk's first record (cls null: the entry carries no name)
+struct RefNote {
+    const uint8_t* stream;
+    uint64_t stream_len;
+    const kwok_watch_frame* frames;
+    uint32_t n_frames;
+    const uint32_t* frame_idx;
+    const uint8_t* cls;
+};
+// one read: items [first, first + n) of a handle list on the device
+struct RefQuery {
+    const int32_t* handles;
+    uint32_t first, n;
+    uint32_t pods;       // KWOK_KIND_PODS (else nodes)
+    uint32_t any_slot;   // the slot's stored bytes whether or not it is live (a freed pod, a tick's delete list)
+    uint64_t* len;       // [n] padded item bytes (k_refs_size), scanned into off
+    uint64_t* off;       // [n]
+    kwok_ref* refs;      // [n]
+    uint8_t* blob;
+};
+constexpr uint32_t REF_NOTE_LANES = 8;    // lanes per record of k_refs_note / k_refs_bind
+constexpr uint32_t REF_GATHER_LANES = 4;  // lanes per item of k_refs_gather
+// behind the apply pass of a pod chunk, next to launch_uid_note (spec: as the pass)
+void launch_refs_note(const DevState& S, const IngestBatch& I, const RefDir& R, const RefNote& N, hipStream_t st);
+void launch_refs_bind(const DevState& S, const RefDir& R, const int32_t* handles, const uint8_t* arena, uint64_t arena_len,
+                      const uint64_t* ns_off, const uint32_t* ns_len, const uint64_t* name_off, const uint32_t* name_len,
+                      uint32_t n, hipStream_t st);
+// every item's status, lengths, padded size and slot (slots[n]); then (after the scan of len into off) refs[] and the blob
+void launch_refs_size(const DevState& S, const RefDir& R, const RefQuery& Q, uint32_t* slots, hipStream_t st);
+size_t refs_scan_bytes(uint32_t n);
+int launch_refs_scan(const RefQuery& Q, void* tmp, size_t tmp_bytes, hipStream_t st);
+void launch_refs_gather(const DevState& S, const RefDir& R, const RefQuery& Q, const uint32_t* slots, hipStream_t st);
+
 }  // namespace kwok

@@ -136,6 +136,11 @@ def declare(lib, pre):
             "ingest_pods_framed_echo": (C.c_int, [VP, VP, U64, VP, SZ, VP, VP, VP, P(SZ), P(SZ), P(SZ)]),
             "ingest_nodes_framed_echo": (C.c_int, [VP, VP, U64, VP, SZ, VP, VP, P(SZ), P(SZ)]),
             "echo_stats": (C.c_int, [VP, VP]),
+            "refs_enable": (C.c_int, [VP]),
+            "refs_bind": (C.c_int, [VP, VP, VP, VP, VP, VP, VP, SZ, P(SZ)]),
+            "refs_lookup": (C.c_int, [VP, C.c_int, VP, SZ, U32, VP, VP, SZ, P(SZ)]),
+            "read_refs": (C.c_int, [VP, C.c_int, SZ, SZ, VP, VP, SZ, P(SZ)]),
+            "refs_stats": (C.c_int, [VP, VP]),
         })
     for name, (res, args) in sig.items():
         f = getattr(lib, pre + name, None)
@@ -843,6 +848,72 @@ class Engine(EngineBase):
         out = (C.c_uint64 * len(abi.ECHO_STATS))()
         self._check(self._lib.kwok_echo_stats(self._h, out), "echo_stats")
         return dict(zip(abi.ECHO_STATS, list(out)))
+
+    # ---- the pod and node reference directory (include/kwok_watch.h): what a patch is addressed to ----
+    def refs_enable(self):
+        """kwok_refs_enable: allocate the directory and the uid directory (idempotent; single-rank engines only)"""
+        self._check(self._lib.kwok_refs_enable(self._h), "refs_enable")
+
+    def refs_bind(self, handles, namespaces, names):
+        """kwok_refs_bind: (namespaces[i], names[i]) become those of live pod handles[i] -> the records that
+        stored nothing"""
+        hs = np.ascontiguousarray(handles, np.int32)
+        n = len(hs)
+        arena, offs, lens = self._uid_spans(list(namespaces) + list(names))
+        assert len(lens) == 2 * n
+        ns_off, nm_off = np.ascontiguousarray(offs[:n]), np.ascontiguousarray(offs[n:])
+        ns_len, nm_len = np.ascontiguousarray(lens[:n]), np.ascontiguousarray(lens[n:])
+        bad = C.c_size_t()
+        rc = self._lib.kwok_refs_bind(self._h, hs.ctypes.data, arena.ctypes.data, ns_off.ctypes.data, ns_len.ctypes.data,
+                                      nm_off.ctypes.data, nm_len.ctypes.data, n, C.byref(bad))
+        self._check(rc, "refs_bind")
+        return bad.value
+
+    def _refs_call(self, what, call, n, blob_cap):
+        """one kwok_refs_lookup / kwok_read_refs: (refs, blob); a blob that proved too small is asked for
+        again with the size the call reported"""
+        refs = np.zeros(n, abi.REF_DTYPE)
+        cap = blob_cap if blob_cap is not None else max(64 * n, 16)
+        for _ in range(2):
+            blob = np.zeros(max(cap, 1), np.uint8)
+            used = C.c_size_t()
+            rc = call(refs.ctypes.data, blob.ctypes.data, cap, C.byref(used))
+            if rc == abi.EINVAL and used.value > cap and blob_cap is None:
+                cap = used.value
+                continue
+            self._check(rc, what)
+            return refs, blob[:used.value]
+        raise AssertionError(what)
+
+    def refs_lookup(self, kind, handles, flags=0, blob_cap=None):
+        """kwok_refs_lookup: the references of handles (abi.KIND_PODS / KIND_NODES) in the caller's order
+        -> (refs as abi.REF_DTYPE rows, blob)"""
+        hs = np.ascontiguousarray(handles, np.int32)
+        return self._refs_call("refs_lookup", lambda r, b, cap, used: self._lib.kwok_refs_lookup(
+            self._h, kind, hs.ctypes.data, len(hs), flags, r, b, cap, used), len(hs), blob_cap)
+
+    def read_refs(self, which, first, count, blob_cap=None):
+        """kwok_read_refs: items [first, first + count) of list `which` (abi.REFS_*) of the last collected
+        tick -> (refs, blob)"""
+        return self._refs_call("read_refs", lambda r, b, cap, used: self._lib.kwok_read_refs(
+            self._h, which, first, count, r, b, cap, used), count, blob_cap)
+
+    @staticmethod
+    def ref_items(refs, blob):
+        """(refs, blob) -> [(status, namespace, name, uid)] with the three as bytes"""
+        raw = blob.tobytes()
+        out = []
+        for off, nsl, nl, ul, st in zip(refs["off"].tolist(), refs["ns_len"].tolist(), refs["name_len"].tolist(),
+                                       refs["uid_len"].tolist(), refs["status"].tolist()):
+            out.append((st, raw[off:off + nsl], raw[off + nsl:off + nsl + nl], raw[off + nsl + nl:off + nsl + nl + ul]))
+        return out
+
+    def refs_stats(self):
+        """kwok_refs_stats: binds / notes stored by ingests / creates without a name / references read /
+        lookups not found / device bytes held"""
+        out = (C.c_uint64 * len(abi.REFS_STATS))()
+        self._check(self._lib.kwok_refs_stats(self._h, out), "refs_stats")
+        return dict(zip(abi.REFS_STATS, list(out)))
 
     @staticmethod
     def _arena_arg(arena):
