@@ -511,6 +511,10 @@ bool parse_time(std::string_view s, int64_t* out) {
     int Y, M, D, h, m, sec;
     if (!d(0, 4, &Y) || !d(5, 2, &M) || !d(8, 2, &D) || !d(11, 2, &h) || !d(14, 2, &m) || !d(17, 2, &sec)) return false;
     if (M < 1 || M > 12 || D < 1 || D > 31 || h > 23 || m > 59 || sec > 59) return false;
+    // a real calendar date (time.Parse: "day out of range"): 30 days in months 4, 6, 9
+    // and 11; February 28, 29 in a Gregorian leap year (json.hip jtime: keep in step)
+    const bool leap = Y % 4 == 0 && (Y % 100 != 0 || Y % 400 == 0);
+    if (D > (M == 2 ? (leap ? 29 : 28) : (M == 4 || M == 6 || M == 9 || M == 11 ? 30 : 31))) return false;
     // days from civil (proleptic Gregorian)
     int y = Y - (M <= 2);
     int era = (y >= 0 ? y : y - 399) / 400;

@@ -305,6 +305,10 @@ __device__ bool jtime(JRd& r, jpos off, uint32_t len, int64_t* out) {
     if (!dg(0, 4, &Y) || !dg(5, 2, &M) || !dg(8, 2, &D) || !dg(11, 2, &hh) || !dg(14, 2, &mm) || !dg(17, 2, &ss))
         return false;
     if (M < 1 || M > 12 || D < 1 || D > 31 || hh > 23 || mm > 59 || ss > 59) return false;
+    // a real calendar date: the month's length, February by the Gregorian leap rule
+    // (codec.cpp parse_time: keep in step)
+    const bool leap = Y % 4 == 0 && (Y % 100 != 0 || Y % 400 == 0);
+    if (D > (M == 2 ? (leap ? 29 : 28) : (M == 4 || M == 6 || M == 9 || M == 11 ? 30 : 31))) return false;
     const int y = Y - (M <= 2);
     const int era = (y >= 0 ? y : y - 399) / 400;
     const int yoe = y - era * 400;

@@ -428,6 +428,10 @@ int kwok_oracle_create(const kwok_config* cfg, kwok_oracle** out) {
         return KWOK_EDOMAIN;
     }
     ip_str(o->node_ip, o->node_ip_s);
+    if (cfg->start_time_unix < 0 || cfg->start_time_unix > 0xFFFFFFFFll) { /* 1970 .. 2106, as the engine */
+        free(o);
+        return KWOK_EDOMAIN;
+    }
     rfc3339(cfg->start_time_unix, o->start_s);
     o->nodes = (onode_t*)calloc((size_t)o->B * o->cn, sizeof(onode_t));
     o->pods = (opod_t*)calloc((size_t)o->B * o->cp, sizeof(opod_t));
@@ -1234,6 +1238,7 @@ int kwok_oracle_tick(kwok_oracle* o, int64_t now_unix, kwok_tick_result* res) {
     const size_t NN = (size_t)o->B * o->cn, NP = (size_t)o->B * o->cp;
     const int T = nthr(o);
     char now[32];
+    if (now_unix < 0 || now_unix > 0xFFFFFFFFll) return KWOK_EDOMAIN; /* as kwok_tick_submit: nothing is ticked */
     rfc3339(now_unix, now);
     uint64_t cnt[KWOK_COUNTER_COUNT] = {0};
     o->arena.n = 0;

@@ -9,6 +9,16 @@ from kwok_amd.engine import Engine, make_config
 from oracle.oracle import Oracle
 
 
+# the source paths of pod patch emission, as the environment that selects each
+# (tests/test_emit_paths_gpu.py's emit_path fixture describes them)
+EMIT_PATHS = {"table": {},
+              "table-fused": {"KWOK_FUSE_EMIT": "1"},
+              "table-fused-k_emit-inits": {"KWOK_FUSE_EMIT": "1", "KWOK_FOLD_INITS": "0"},
+              "table-unfused": {"KWOK_FUSE_EMIT": "0"},
+              "general": {"KWOK_EMIT_TAB_UNITS": "0"},
+              "mixed": {"KWOK_EMIT_TAB_UNITS": "20000"}}
+
+
 def compare(e_out, o_out, where):
     assert list(e_out.heartbeat_nodes) == list(o_out.heartbeat_nodes), where + " heartbeat handles"
     n = len(e_out.heartbeat_nodes)

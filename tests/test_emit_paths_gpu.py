@@ -14,14 +14,13 @@ decades, and empty / non-empty statuses."""
 import numpy as np
 import pytest
 
-from gpu_common import Driver, new_pods
+from gpu_common import EMIT_PATHS, Driver, new_pods
 from kwok_amd import abi
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(autouse=True, params=["table", "table-fused", "table-fused-k_emit-inits", "table-unfused", "general",
-                                      "mixed"])
+@pytest.fixture(autouse=True, params=list(EMIT_PATHS))
 def emit_path(request, monkeypatch):
     """pod patches from the per-shape unit tables (on split ticks written by
     k_pod_jobs itself, the fused emission, when the tick is dense, its last
@@ -31,17 +30,8 @@ def emit_path(request, monkeypatch):
     job records, KWOK_FUSE_EMIT=0), from the general region emitter
     (KWOK_EMIT_TAB_UNITS=0), or both (a cap that tables only the first specs
     registered, so chunks mix the two and fall back as a whole; no fusion)"""
-    if request.param == "table-fused":
-        monkeypatch.setenv("KWOK_FUSE_EMIT", "1")
-    elif request.param == "table-fused-k_emit-inits":
-        monkeypatch.setenv("KWOK_FUSE_EMIT", "1")
-        monkeypatch.setenv("KWOK_FOLD_INITS", "0")
-    elif request.param == "table-unfused":
-        monkeypatch.setenv("KWOK_FUSE_EMIT", "0")
-    elif request.param == "general":
-        monkeypatch.setenv("KWOK_EMIT_TAB_UNITS", "0")
-    elif request.param == "mixed":
-        monkeypatch.setenv("KWOK_EMIT_TAB_UNITS", "20000")
+    for k, v in EMIT_PATHS[request.param].items():
+        monkeypatch.setenv(k, v)
     return request.param
 
 HOST_IPS = ["1.2.3.4", "10.20.30.40", "100.100.100.100", "192.168.100.200", "255.255.255.255", "9.99.9.99"]
