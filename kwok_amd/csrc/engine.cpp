@@ -39,6 +39,7 @@
 #include "kernels.h"
 #include "echo.h"
 #include "templates.h"
+#include "engine_impl.h"
 
 using namespace kwok;
 
@@ -199,22 +200,26 @@ struct kwok_engine {
     size_t d_ops_cap = 0;
 
     // ---- GPU pod ingest (ingest.hip) ----
-    struct Ingest {
-        size_t cap = 0;          // records the per-record buffers hold
-        size_t arena_cap = 0;
+    struct KWOK_LOCAL Ingest {
         size_t sort_bytes = 0;
-        void* d_ev = nullptr;
-        uint8_t* d_arena = nullptr;
-        PodRec* rec = nullptr;
-        uint32_t *keys = nullptr, *keys_sorted = nullptr, *idx_sorted = nullptr;
-        int32_t *out_handle = nullptr, *out_status = nullptr;
-        int8_t* out_status8 = nullptr;  // kwok_ingest_pods_packed: the statuses as bytes
-        uint32_t* out_released = nullptr;
-        void* sort_tmp = nullptr;
+        DevArr<void> d_ev;       // [recs.cap] kwok_pod_event, or the packed forms
+        DevArr<uint8_t> d_arena;
+        DevArr<PodRec> rec;
+        DevArr<uint32_t> keys, keys_sorted, idx_sorted;
+        DevArr<int32_t> out_handle, out_status;
+        DevArr<int8_t> out_status8;  // kwok_ingest_pods_packed: the statuses as bytes
+        DevArr<uint32_t> out_released;
+        DevArr<void> sort_tmp;   // [sort_bytes]
         // kwok_ingest_pods_packed12: NEW records per 256-record tile, the tiles' prefixes,
         // the creates' handles in create order
-        uint32_t *tile_new = nullptr, *tile_pre = nullptr;
-        int32_t* new_handle = nullptr;
+        DevArr<uint32_t> tile_new, tile_pre;
+        DevArr<int32_t> new_handle;
+        static size_t ev_bytes(size_t cap) { return cap * sizeof(kwok_pod_event); }
+        static size_t sort_need(size_t cap) { return ingest_sort_bytes((uint32_t)cap, 32); }
+        // the per-record buffers (recs.cap: the records they hold) and the batch's strings
+        DevGroup recs{4096, {{d_ev, ev_bytes}, rec, keys, keys_sorted, idx_sorted, out_handle, out_status, out_released,
+                             out_status8, {tile_new, per_tile256}, {tile_pre, per_tile256}, new_handle, {sort_tmp, sort_need}}};
+        DevGroup arena{1 << 16, {d_arena}};
         // per bucket (allocated once)
         uint32_t *beg = nullptr, *end = nullptr;
         uint32_t* abort = nullptr;          // [1] a chunk of the batch needs growth (speculative apply passes)
@@ -223,15 +228,16 @@ struct kwok_engine {
         size_t nsums = 0;
         IngSummary* sum = nullptr;
         // node batches (kwok_ingest_nodes): records, names, prepared records, host list
-        size_t ncap = 0;
-        kwok_node_event* d_nev = nullptr;
-        uint8_t* d_nnames = nullptr;  // [ncap * NAME_STRIDE]
-        NodeRec* nrec = nullptr;
-        uint32_t* host_idx = nullptr;
-        NodeFix* d_nfix = nullptr;
+        DevArr<kwok_node_event> d_nev;
+        DevArr<uint8_t> d_nnames;  // [nodes.cap * NAME_STRIDE]
+        DevArr<NodeRec> nrec;
+        DevArr<uint32_t> host_idx;
+        DevArr<NodeFix> d_nfix;
+        static size_t name_bytes(size_t cap) { return cap * NAME_STRIDE; }
+        DevGroup nodes{4096, {d_nev, {d_nnames, name_bytes}, nrec, host_idx, d_nfix}};
         NodeSummary* nsum = nullptr;
         NodeSummary* nsum_h = nullptr;  // pinned
-        int32_t* res_h = nullptr;       // pinned [2 * ncap]: handles, statuses
+        Pinned<int32_t> res_h;          // [2 * nodes.cap]: handles, statuses
         IngSummary* sum_h = nullptr;  // pinned
         // a batch runs in chunks (KWOK_INGEST_CHUNK records): chunk k+1's prep reads its
         // records over the link on `pst` while chunk k is applied and its results copied
@@ -251,182 +257,187 @@ struct kwok_engine {
     // ---- the watch stream framer (json.hip k_frame_*): the resident stream, its
     // frames on the device and on the host, the caller's bytes (listed lines and
     // documents are completed from them) ----
-    struct Watch {
-        uint8_t* stream = nullptr;     // [cap] the stream, padded to whole 16-byte windows
-        size_t cap = 0;
+    struct KWOK_LOCAL Watch {
+        DevArr<uint8_t> stream;        // [bytes.cap] the stream, padded to whole 16-byte windows
+        DevGroup bytes{1 << 16, {stream}};
         uint64_t len = 0;
         const char* host = nullptr;    // the caller's buffer (valid until the next framing call)
-        uint32_t *tile_cnt = nullptr, *tile_base = nullptr;
-        size_t tile_cap = 0;
-        uint32_t* ends = nullptr;      // [fcap] newline offsets
-        kwok_watch_frame* frames = nullptr;  // [fcap]
-        uint32_t* host_list = nullptr; // [fcap]
-        size_t fcap = 0;
-        uint32_t* counts = nullptr;    // device [2]: newlines, listed lines
-        uint32_t* counts_h = nullptr;  // pinned [2]
+        DevArr<uint32_t> tile_cnt, tile_base;
+        DevGroup tiles{1024, {tile_cnt, tile_base}};
+        DevArr<uint32_t> ends;         // [lines.cap] newline offsets
+        DevArr<kwok_watch_frame> frames;  // [lines.cap]
+        DevArr<uint32_t> host_list;    // [lines.cap]
+        DevGroup lines{4096, {ends, frames, host_list}};
+        DevArr<uint32_t> counts;       // [2]: newlines, listed lines
+        Pinned<uint32_t> counts_h;     // [2]
         std::vector<kwok_watch_frame> frames_h;
         uint64_t id = 0, next_id = 1;  // id 0: no stream resident
         uint64_t stats[KWOK_WATCH_STAT_COUNT] = {};
         // the List body framer (json.hip k_list_*): eight arrays of per-tile words,
         // the candidates' `{` offsets (their `}` go to ends), its counters
-        uint32_t* ltile = nullptr;     // [8][ltile_cap]
-        size_t ltile_cap = 0;
-        uint32_t* starts = nullptr;    // [scap]
-        size_t scap = 0;
-        uint32_t* lc = nullptr;        // device [KWOK_LIST_COUNTERS]
-        uint32_t* lc_h = nullptr;      // pinned [KWOK_LIST_COUNTERS]
+        DevArr<uint32_t> ltile;        // [8][ltiles.cap]
+        static size_t eight(size_t cap) { return 8 * cap; }
+        DevGroup ltiles{1024, {{ltile, eight}}};
+        DevArr<uint32_t> starts;       // [cands.cap]
+        DevGroup cands{4096, {starts}};
+        DevArr<uint32_t> lc;           // [KWOK_LIST_COUNTERS]
+        Pinned<uint32_t> lc_h;         // [KWOK_LIST_COUNTERS]
         uint64_t lstats[KWOK_LIST_STAT_COUNT] = {};
     } watch;
 
     // ---- relist with Replace (resync.hip, kwok_watch.h): a `seen` byte per slot of each
     // kind (allocated at the kind's first begin), the sweep's tile counts and outputs ----
-    struct Resync {
-        uint8_t* pod_seen = nullptr;   // [PLa] re-laid out with the pod arrays (grow_pods)
-        uint8_t* node_seen = nullptr;  // [NLa]
+    struct KWOK_LOCAL Resync {
+        DevArr<uint8_t> pod_seen;      // [PLa] re-laid out with the pod arrays (grow_pods)
+        DevArr<uint8_t> node_seen;     // [NLa]
         bool open[2] = {false, false}; // KWOK_KIND_*: a session is open (the ingests mark)
-        ResyncCounters* ctr = nullptr;    // device
-        ResyncCounters* ctr_h = nullptr;  // pinned
-        uint32_t *tile_cnt = nullptr, *tile_base = nullptr;
-        size_t tile_cap = 0;
-        uint32_t* total = nullptr;     // device [1]
-        uint32_t* total_h = nullptr;   // pinned [1]
-        int32_t *d_handles = nullptr, *d_nodes = nullptr;  // [out_cap] the swept handles / their nodes, emit order
-        size_t out_cap = 0;
-        int32_t* d_mark = nullptr;     // [mark_cap] kwok_resync_mark's handles
-        size_t mark_cap = 0;
+        DevArr<ResyncCounters> ctr;
+        Pinned<ResyncCounters> ctr_h;
+        DevArr<uint32_t> tile_cnt, tile_base;
+        DevGroup tiles{1024, {tile_cnt, tile_base}};
+        DevArr<uint32_t> total;        // [1]
+        Pinned<uint32_t> total_h;      // [1]
+        DevArr<int32_t> d_handles, d_nodes;  // [swept.cap] the swept handles / their nodes, emit order
+        DevGroup swept{4096, {d_handles, d_nodes}};
+        DevArr<int32_t> d_mark;        // [marks.cap] kwok_resync_mark's handles
+        DevGroup marks{4096, {d_mark}};
         uint64_t stats[KWOK_RESYNC_STAT_COUNT] = {};
     } resync;
 
     // ---- the pod uid directory (uid.hip, kwok_watch.h): a uid per pod slot, the table
     // of hints, the per-call buffers of a by-uid framed batch and of bind / lookup ----
-    struct Uid {
+    struct KWOK_LOCAL Uid {
         struct Bytes {
             uint8_t b[KWOK_UID_MAX];
         };
         bool on = false;
-        Bytes* pod_uid = nullptr;        // [PLa] re-laid out with the pod arrays (grow_pods)
-        uint8_t* pod_uid_len = nullptr;  // [PLa]
-        unsigned long long* tab = nullptr;
+        DevArr<Bytes> pod_uid;           // [PLa] re-laid out with the pod arrays (grow_pods)
+        DevArr<uint8_t> pod_uid_len;     // [PLa]
+        DevArr<unsigned long long> tab;
         size_t tab_cap = 0;              // entries (a power of two)
         int forced_log2 = 0;             // KWOK_UID_TAB_LOG2 (tests)
         uint64_t live = 0, inserted = 0; // entries at the last rebuild; an upper bound of the inserts since
-        UidCounters* ctr = nullptr;      // device
-        UidCounters* ctr_h = nullptr;    // pinned
-        UidRun* run = nullptr;           // device
-        UidRun* run_h = nullptr;         // pinned
+        DevArr<UidCounters> ctr;
+        Pinned<UidCounters> ctr_h;
+        DevArr<UidRun> run;
+        Pinned<UidRun> run_h;
         // per record of a by-uid batch
-        size_t cap = 0;
-        uint32_t *fidx = nullptr, *uoff = nullptr, *res_rel = nullptr;
-        uint8_t *ulen = nullptr, *cls = nullptr;
-        uint64_t* hash = nullptr;
-        int32_t *res_h = nullptr, *res_st = nullptr;
-        uint32_t* claim = nullptr;
-        size_t claim_cap = 0;
+        DevArr<uint32_t> fidx, uoff, res_rel;
+        DevArr<uint8_t> ulen, cls;
+        DevArr<uint64_t> hash;
+        DevArr<int32_t> res_h, res_st;
+        DevGroup recs{4096, {fidx, uoff, res_rel, ulen, cls, hash, res_h, res_st}};
+        DevArr<uint32_t> claim;
+        DevGroup claims{0, {claim}};     // (sized by claim_size: no headroom)
         // bind / lookup: handles or results, spans, the caller's arena
-        size_t qcap = 0, acap = 0;
-        int32_t* q_h = nullptr;
-        uint64_t* q_off = nullptr;
-        uint32_t* q_len = nullptr;
-        uint8_t* q_arena = nullptr;
+        DevArr<int32_t> q_h;
+        DevArr<uint64_t> q_off;
+        DevArr<uint32_t> q_len;
+        DevGroup spans{4096, {q_h, q_off, q_len}};
+        DevArr<uint8_t> q_arena;
+        DevGroup arena{1 << 16, {q_arena}};
         // the by-uid batch whose records the ingest is applying (null: an entry that carries no uid)
         const UidNote* note = nullptr;
         std::vector<hipEvent_t> note_ev;  // KWOK_INGEST_PROF: stamps around each k_uid_note of a by-uid batch, in pairs
         uint64_t stats[KWOK_UID_STAT_COUNT] = {};
-        UidDir dir() const { return UidDir{reinterpret_cast<uint8_t*>(pod_uid), pod_uid_len, tab, (uint32_t)(tab_cap - 1), ctr}; }
+        UidDir dir() const { return UidDir{reinterpret_cast<uint8_t*>(pod_uid.p), pod_uid_len, tab, (uint32_t)(tab_cap - 1), ctr}; }
     } uid;
 
     // ---- the echo ledger (echo.hip, kwok_watch.h): the pool of noted uids behind its table,
     // the per-call buffers of a filtered batch ----
-    struct Echo {
+    struct KWOK_LOCAL Echo {
         bool on = false;
-        uint32_t* tab = nullptr;
+        DevArr<uint32_t> tab;
         size_t tab_cap = 0;           // entries (a power of two)
-        EchoEntry* pool = nullptr;
+        DevArr<EchoEntry> pool;
         size_t pool_cap = 0;
         int forced_log2 = 0;          // KWOK_ECHO_TAB_LOG2 (tests)
-        EchoCounters* ctr = nullptr;  // device
-        EchoCounters* ctr_h = nullptr;  // pinned: the counters after the last call
-        EchoCall* call = nullptr;     // device
-        EchoCall* call_h = nullptr;   // pinned
+        DevArr<EchoCounters> ctr;
+        Pinned<EchoCounters> ctr_h;   // the counters after the last call
+        DevArr<EchoCall> call;
+        Pinned<EchoCall> call_h;
         uint64_t rebuilds = 0;
         // per record of a call
-        size_t cap = 0;
-        uint32_t *uoff = nullptr, *roff = nullptr, *own = nullptr, *cnt = nullptr, *fill = nullptr, *lbase = nullptr,
-                 *list = nullptr, *fidx = nullptr, *bsum = nullptr, *kidx = nullptr, *kpos = nullptr, *q_len = nullptr,
-                 *res_rel = nullptr;
-        uint8_t *ulen = nullptr, *rlen = nullptr, *kind = nullptr, *res = nullptr;
-        uint64_t *hash = nullptr, *q_off = nullptr;
-        int32_t *hdrop = nullptr, *res_h = nullptr, *res_st = nullptr;
-        uint32_t* claim = nullptr;
-        size_t claim_cap = 0;
+        DevArr<uint32_t> uoff, roff, own, cnt, fill, lbase, list, fidx, bsum, kidx, kpos, q_len, res_rel;
+        DevArr<uint8_t> ulen, rlen, kind, res;
+        DevArr<uint64_t> hash, q_off;
+        DevArr<int32_t> hdrop, res_h, res_st;
+        DevGroup recs{4096, {uoff, roff, own, cnt, fill, lbase, list, fidx, {bsum, per_tile256}, kidx, kpos, q_len, res_rel,
+                             ulen, rlen, kind, res, hash, q_off, hdrop, res_h, res_st}};
+        DevArr<uint32_t> claim;
+        DevGroup claims{0, {claim}};  // (sized by claim_size: no headroom)
         // the typed front end: spans, ops, statuses and the caller's arena
-        size_t scap = 0, acap = 0;
-        uint64_t *s_uoff = nullptr, *s_roff = nullptr;
-        uint32_t *s_ulen = nullptr, *s_rlen = nullptr;
-        uint8_t* s_op = nullptr;
-        int32_t* s_status = nullptr;
-        uint8_t* arena = nullptr;
+        DevArr<uint64_t> s_uoff, s_roff;
+        DevArr<uint32_t> s_ulen, s_rlen;
+        DevArr<uint8_t> s_op;
+        DevArr<int32_t> s_status;
+        DevGroup spans{4096, {s_uoff, s_roff, s_ulen, s_rlen, s_op, s_status}};
+        DevArr<uint8_t> arena;
+        DevGroup bytes{1 << 16, {arena}};
         EchoLedger ledger() const { return EchoLedger{tab, (uint32_t)(tab_cap - 1), pool, (uint32_t)pool_cap, ctr}; }
     } echo;
 
     // ---- the pod and node reference directory (refs.hip, kwok_watch.h): namespace and name per pod
     // slot, the per-call buffers of bind / lookup / read ----
-    struct Refs {
+    struct KWOK_LOCAL Refs {
         struct Bytes {
             uint8_t b[KWOK_REF_STRIDE];
         };
         bool on = false;
-        Bytes* pod_ref = nullptr;         // [PLa] re-laid out with the pod arrays (grow_pods)
-        uint16_t* pod_ref_len = nullptr;  // [PLa]
-        RefCounters* ctr = nullptr;       // device
-        RefCounters* ctr_h = nullptr;     // pinned
+        DevArr<Bytes> pod_ref;            // [PLa] re-laid out with the pod arrays (grow_pods)
+        DevArr<uint16_t> pod_ref_len;     // [PLa]
+        DevArr<RefCounters> ctr;
+        Pinned<RefCounters> ctr_h;
         // the stale guard: per kind (KWOK_KIND_*), bumped by every call that can create an object of it
         uint64_t gen[2] = {0, 0};
         // lookup / read: handles, sizes, offsets, slots, references, the scan's storage, the blob
-        size_t qcap = 0, tmp_bytes = 0, blob_cap = 0;
-        int32_t* q_h = nullptr;
-        uint64_t *q_len = nullptr, *q_off = nullptr;
-        uint32_t* q_slot = nullptr;
-        kwok_ref* q_refs = nullptr;
-        void* q_tmp = nullptr;
-        uint8_t* q_blob = nullptr;
-        // bind: the spans (namespaces, then names) and the caller's arena
-        size_t bcap = 0, acap = 0;
-        uint64_t* b_off = nullptr;
-        uint32_t* b_len = nullptr;
-        uint8_t* b_arena = nullptr;
+        DevArr<uint64_t> q_len, q_off;
+        DevArr<uint32_t> q_slot;
+        DevArr<kwok_ref> q_refs;
+        DevGroup items{4096, {q_len, q_off, q_slot, q_refs}};
+        DevArr<void> q_tmp;               // [tmp_bytes] (not zero-filled)
+        size_t tmp_bytes = 0;
+        DevArr<uint8_t> q_blob;
+        DevGroup blob{1 << 16, {q_blob}};
+        // bind: the spans (namespaces, then names), the handles (lookup's too) and the caller's arena
+        DevArr<uint64_t> b_off;
+        DevArr<uint32_t> b_len;
+        DevArr<int32_t> q_h;
+        DevGroup spans{4096, {{b_off, twice}, {b_len, twice}, q_h}};
+        DevArr<uint8_t> b_arena;
+        DevGroup arena{1 << 16, {b_arena}};
         // the by-uid batch whose records the ingest is applying (null: an entry that carries no name)
         const RefNote* note = nullptr;
     } refs;
     RefDir ref_dir() const {
-        return RefDir{reinterpret_cast<uint8_t*>(refs.pod_ref), refs.pod_ref_len, reinterpret_cast<const uint8_t*>(uid.pod_uid),
+        return RefDir{reinterpret_cast<uint8_t*>(refs.pod_ref.p), refs.pod_ref_len, reinterpret_cast<const uint8_t*>(uid.pod_uid.p),
                       uid.pod_uid_len, refs.ctr};
     }
 
     // ---- the pod codec on the GPU (json.hip): per-document buffers, the codec's
     // selectors, the spec table (kwok_spec_key -> spec id) ----
-    struct Json {
-        size_t cap = 0;
-        uint64_t* off = nullptr;
-        uint32_t* len = nullptr;
-        uint8_t* op = nullptr;
-        int32_t* handle = nullptr;
-        JsonPodSide* side = nullptr;
-        uint32_t* host_list = nullptr;
-        kwok_pod_event* fix_ev = nullptr;  // the listed documents' records (gathered, completed, scattered)
-        JsonPodSide* fix_side = nullptr;
-        uint32_t* n_host = nullptr;        // device [1]
-        uint32_t* n_host_h = nullptr;      // pinned [1]
-        JsonCfg* cfg = nullptr;
-        JsonCfg* cfg_h = nullptr;          // pinned staging
-        uint64_t* tab_key = nullptr;
-        int32_t* tab_id = nullptr;
-        int32_t* nstat = nullptr;          // node documents: the device decode's status per document
-        kwok_node_event* nev_fix = nullptr;  // node records gathered for / scattered from the host
-        size_t ncap = 0;
-        uint2* tab_canon = nullptr;        // per slot: offset / length of its spec's canonical string in canon
-        uint8_t* canon = nullptr;          // the registered specs' canonical strings (json_spec_canon)
-        size_t canon_cap = 0;
+    struct KWOK_LOCAL Json {
+        DevArr<uint64_t> off;
+        DevArr<uint32_t> len;
+        DevArr<uint8_t> op;
+        DevArr<int32_t> handle;
+        DevArr<JsonPodSide> side;
+        DevArr<uint32_t> host_list;
+        DevArr<kwok_pod_event> fix_ev;     // the listed documents' records (gathered, completed, scattered)
+        DevArr<JsonPodSide> fix_side;
+        DevGroup docs{4096, {off, len, op, handle, side, host_list, fix_ev, fix_side}};
+        DevArr<uint32_t> n_host;           // [1]
+        Pinned<uint32_t> n_host_h;         // [1]
+        DevArr<JsonCfg> cfg;
+        Pinned<JsonCfg> cfg_h;             // staging
+        DevArr<uint64_t> tab_key;
+        DevArr<int32_t> tab_id;
+        DevArr<int32_t> nstat;             // node documents: the device decode's status per document
+        DevArr<kwok_node_event> nev_fix;   // node records gathered for / scattered from the host
+        DevGroup node_docs{4096, {nstat, nev_fix}};
+        DevArr<uint2> tab_canon;           // per slot: offset / length of its spec's canonical string in canon
+        DevArr<uint8_t> canon;             // the registered specs' canonical strings (json_spec_canon)
+        DevGroup canon_bytes{4096, {canon}};
         uint32_t tab_mask = 0;
         bool tab_dirty = true;
     } json;
@@ -708,6 +719,29 @@ int dgrow(kwok_engine* e, DevBuf<T>& b, size_t n) {
     b.n = cap;
     return KWOK_OK;
 }
+
+template <class T>
+int dalloc(kwok_engine* e, DevArr<T>* a, size_t n) {
+    return dalloc(e, &a->p, n);
+}
+template <class T>
+void dfree(DevArr<T>& a) {
+    a.release();
+}
+
+}  // namespace
+
+int kwok::DevGroup::reserve(kwok_engine* e, size_t need, size_t want) {
+    if (need <= cap) return KWOK_OK;
+    release();
+    const size_t c = std::max(want, floor_);
+    for (auto& m : m_)
+        if (int rc = dalloc(e, (uint8_t**)m.p, std::max<size_t>(m.count ? m.count(c) : c, 1) * m.elem)) return rc;
+    cap = c;
+    return KWOK_OK;
+}
+
+namespace {
 
 int ensure_pinned(kwok_engine* e, size_t bytes) {
     if (bytes <= e->pinned_cap) return KWOK_OK;
@@ -1011,12 +1045,12 @@ int grow_pods(kwok_engine* e, uint32_t new_cp) {
         (rc = relayout(S.pod_ctime)) || (rc = relayout(S.pod_ip)) || (rc = relayout(S.host_ip)) ||
         (rc = resize(S.alloc_addr, false)) || (rc = resize(S.use_list, false)) || (rc = resize(S.rel_list, false)))
         return rc;
-    if (e->resync.pod_seen && (rc = relayout(e->resync.pod_seen))) return rc;  // (a growth inside a session keeps the marks)
+    if (e->resync.pod_seen && (rc = relayout(e->resync.pod_seen.p))) return rc;  // (a growth inside a session keeps the marks)
     // the uid directory's per-slot uids move with their pods (handles are stable; the table is rebuilt
     // to the new size before its next use, uid_ensure)
-    if (e->uid.on && ((rc = relayout(e->uid.pod_uid)) || (rc = relayout(e->uid.pod_uid_len)))) return rc;
+    if (e->uid.on && ((rc = relayout(e->uid.pod_uid.p)) || (rc = relayout(e->uid.pod_uid_len.p)))) return rc;
     // ... and the reference directory's namespaces and names
-    if (e->refs.on && ((rc = relayout(e->refs.pod_ref)) || (rc = relayout(e->refs.pod_ref_len)))) return rc;
+    if (e->refs.on && ((rc = relayout(e->refs.pod_ref.p)) || (rc = relayout(e->refs.pod_ref_len.p)))) return rc;
     for (auto& T : e->slots) {
         if (!T.alloc) continue;
         if ((rc = resize(T.pp_pods, true)) || (rc = resize(T.pp_off, true)) || (rc = resize(T.pp_len, true)) ||
@@ -1040,40 +1074,10 @@ uint32_t sort_bits(const kwok_engine* e) {  // sort keys are local buckets 0..nb
 // per-record device buffers for batches of n records (grown with headroom)
 int ingest_reserve(kwok_engine* e, size_t n, size_t arena_len) {
     auto& G = e->ing;
-    if (n > G.cap) {
-        const size_t cap = std::max<size_t>(n + n / 4, 4096);
-        void* ptrs[] = {G.d_ev, G.rec, G.keys, G.keys_sorted, G.idx_sorted, G.out_handle, G.out_status,
-                        G.out_released, G.sort_tmp, G.out_status8, G.tile_new, G.tile_pre, G.new_handle};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-        G.d_ev = G.sort_tmp = nullptr;
-        G.tile_new = G.tile_pre = nullptr;
-        G.new_handle = nullptr;
-        G.out_status8 = nullptr;
-        G.rec = nullptr;
-        G.keys = G.keys_sorted = G.idx_sorted = G.out_released = nullptr;
-        G.out_handle = G.out_status = nullptr;
-        G.cap = G.sort_bytes = 0;
-        int rc = 0;
-        if ((rc = dalloc(e, (uint8_t**)&G.d_ev, cap * sizeof(kwok_pod_event))) || (rc = dalloc(e, &G.rec, cap)) ||
-            (rc = dalloc(e, &G.keys, cap)) || (rc = dalloc(e, &G.keys_sorted, cap)) || (rc = dalloc(e, &G.idx_sorted, cap)) ||
-            (rc = dalloc(e, &G.out_handle, cap)) || (rc = dalloc(e, &G.out_status, cap)) ||
-            (rc = dalloc(e, &G.out_released, cap)) || (rc = dalloc(e, &G.out_status8, cap)) ||
-            (rc = dalloc(e, &G.tile_new, cap / 256 + 2)) || (rc = dalloc(e, &G.tile_pre, cap / 256 + 2)) ||
-            (rc = dalloc(e, &G.new_handle, cap)))
-            return rc;
-        G.sort_bytes = ingest_sort_bytes((uint32_t)cap, 32);
-        if ((rc = dalloc(e, (uint8_t**)&G.sort_tmp, G.sort_bytes))) return rc;
-        G.cap = cap;
-    }
-    if (arena_len > G.arena_cap) {
-        if (G.d_arena) (void)hipFree(G.d_arena);
-        G.d_arena = nullptr;
-        G.arena_cap = 0;
-        const size_t cap = std::max<size_t>(arena_len + arena_len / 4, 1 << 16);
-        if (int rc = dalloc(e, &G.d_arena, cap)) return rc;
-        G.arena_cap = cap;
-    }
+    int rc = G.recs.reserve(e, n);
+    G.sort_bytes = G.recs.cap ? G.sort_need(G.recs.cap) : 0;
+    if (rc) return rc;
+    if ((rc = G.arena.reserve(e, arena_len))) return rc;
     return KWOK_OK;
 }
 IngestBatch ingest_batch(kwok_engine* e, uint32_t n, size_t arena_len) {
@@ -1308,86 +1312,28 @@ void kwok_engine_destroy(kwok_engine* e) {
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (auto& T : e->slots) free_slot(T);
-    {
-        auto& g = e->ing;
-        void* ip[] = {g.d_ev, g.d_arena, g.rec, g.keys, g.keys_sorted, g.idx_sorted, g.out_handle, g.out_status,
-                      g.out_released, g.sort_tmp, g.abort, g.sums, g.beg, g.end, g.sum, g.sum1, g.tile_new, g.tile_pre,
-                      g.new_handle,
-                      g.out_status8, g.d_nev, g.d_nnames, g.nrec, g.host_idx, g.d_nfix, g.nsum};
-        for (void* p : ip)
-            if (p) (void)hipFree(p);
-        if (g.sum_h) (void)hipHostFree(g.sum_h);
-        if (g.nsum_h) (void)hipHostFree(g.nsum_h);
-        if (g.sums_h) (void)hipHostFree(g.sums_h);
-        if (g.res_h) (void)hipHostFree(g.res_h);
-        hipEvent_t evs[] = {g.go, g.prepped[0], g.prepped[1], g.used[0], g.used[1], g.rdone, g.idone};
-        for (hipEvent_t x : evs)
-            if (x) (void)hipEventDestroy(x);
-        if (g.pst) (void)hipStreamDestroy(g.pst);
-        if (g.dst) (void)hipStreamDestroy(g.dst);
-    }
-    {
-        auto& J = e->json;
-        void* jp[] = {J.off, J.len, J.op, J.handle, J.side, J.host_list, J.fix_ev, J.fix_side, J.n_host, J.cfg,
-                      J.tab_key, J.tab_id, J.tab_canon, J.canon, J.nstat, J.nev_fix};
-        for (void* p : jp)
-            if (p) (void)hipFree(p);
-        if (J.cfg_h) (void)hipHostFree(J.cfg_h);
-        if (J.n_host_h) (void)hipHostFree(J.n_host_h);
-    }
-    {
-        auto& Wt = e->watch;
-        void* wp[] = {Wt.stream, Wt.tile_cnt, Wt.tile_base, Wt.ends, Wt.frames, Wt.host_list, Wt.counts,
-                      Wt.ltile, Wt.starts, Wt.lc};
-        for (void* p : wp)
-            if (p) (void)hipFree(p);
-        if (Wt.counts_h) (void)hipHostFree(Wt.counts_h);
-        if (Wt.lc_h) (void)hipHostFree(Wt.lc_h);
-    }
-    {
-        auto& R = e->resync;
-        void* rp[] = {R.pod_seen, R.node_seen, R.ctr, R.tile_cnt, R.tile_base, R.total, R.d_handles, R.d_nodes, R.d_mark};
-        for (void* p : rp)
-            if (p) (void)hipFree(p);
-        if (R.ctr_h) (void)hipHostFree(R.ctr_h);
-        if (R.total_h) (void)hipHostFree(R.total_h);
-    }
-    {
-        auto& U = e->uid;
-        void* up[] = {U.pod_uid, U.pod_uid_len, U.tab, U.ctr, U.run, U.fidx, U.uoff, U.res_rel, U.ulen, U.cls, U.hash,
-                      U.res_h, U.res_st, U.claim, U.q_h, U.q_off, U.q_len, U.q_arena};
-        for (void* p : up)
-            if (p) (void)hipFree(p);
-        if (U.ctr_h) (void)hipHostFree(U.ctr_h);
-        if (U.run_h) (void)hipHostFree(U.run_h);
-    }
-    {
-        auto& R = e->refs;
-        void* rp[] = {R.pod_ref, R.pod_ref_len, R.ctr, R.q_h, R.q_len, R.q_off, R.q_slot, R.q_refs, R.q_tmp, R.q_blob, R.b_off,
-                      R.b_len, R.b_arena};
-        for (void* p : rp)
-            if (p) (void)hipFree(p);
-        if (R.ctr_h) (void)hipHostFree(R.ctr_h);
-    }
-    {
-        auto& E = e->echo;
-        void* ep[] = {E.tab, E.pool, E.ctr, E.call, E.uoff, E.roff, E.own, E.cnt, E.fill, E.lbase, E.list, E.fidx, E.bsum,
-                      E.kidx, E.kpos, E.q_len, E.res_rel, E.ulen, E.rlen, E.kind, E.res, E.hash, E.q_off, E.hdrop, E.res_h,
-                      E.res_st, E.claim, E.s_uoff, E.s_roff, E.s_ulen, E.s_rlen, E.s_op, E.s_status, E.arena};
-        for (void* p : ep)
-            if (p) (void)hipFree(p);
-        if (E.ctr_h) (void)hipHostFree(E.ctr_h);
-        if (E.call_h) (void)hipHostFree(E.call_h);
-    }
+    // (the scratch of the ingests, the codec, the framers and the directories owns itself: freed with the engine below)
+    auto& g = e->ing;
+    void* ip[] = {g.abort, g.sums, g.beg, g.end, g.sum, g.sum1, g.nsum};
+    for (void* p : ip)
+        if (p) (void)hipFree(p);
+    if (g.sum_h) (void)hipHostFree(g.sum_h);
+    if (g.nsum_h) (void)hipHostFree(g.nsum_h);
+    if (g.sums_h) (void)hipHostFree(g.sums_h);
+    hipEvent_t evs[] = {g.go, g.prepped[0], g.prepped[1], g.used[0], g.used[1], g.rdone, g.idone};
+    for (hipEvent_t x : evs)
+        if (x) (void)hipEventDestroy(x);
     if (e->h_xall) (void)hipHostFree(e->h_xall);
     if (e->pinned) (void)hipHostFree(e->pinned);
     if (e->dump_h) (void)hipHostFree(e->dump_h);
     if (e->comm) ncclCommDestroy(e->comm);
     if (e->d_pod_fill) (void)hipFree(e->d_pod_fill);
     if (e->fence) (void)hipEventDestroy(e->fence);
-    if (e->rst) (void)hipStreamDestroy(e->rst);
-    if (e->st) (void)hipStreamDestroy(e->st);
+    // the engine's members free their device and pinned memory here, while the streams still exist
+    const hipStream_t streams[] = {g.pst, g.dst, e->rst, e->st};
     delete e;
+    for (hipStream_t x : streams)
+        if (x) (void)hipStreamDestroy(x);
 }
 
 int kwok_engine_create(const kwok_config* cfg, kwok_engine** out) {
@@ -1831,20 +1777,13 @@ int kwok_register_pod_spec(kwok_engine* e, const kwok_pod_spec* spec, const char
 int node_reserve(kwok_engine* e, size_t n, size_t arena_len) {
     auto& G = e->ing;
     if (int rc = ingest_reserve(e, n, arena_len)) return rc;
-    if (n <= G.ncap) return KWOK_OK;
-    void* ptrs[] = {G.d_nev, G.d_nnames, G.nrec, G.host_idx, G.d_nfix};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (G.res_h) (void)hipHostFree(G.res_h);
-    G.d_nev = nullptr, G.d_nnames = nullptr, G.nrec = nullptr, G.host_idx = nullptr, G.d_nfix = nullptr, G.res_h = nullptr;
-    G.ncap = 0;
-    const size_t cap = std::max<size_t>(n + n / 4, 4096);
-    int rc = 0;
-    if ((rc = dalloc(e, &G.d_nev, cap)) || (rc = dalloc(e, &G.d_nnames, cap * NAME_STRIDE)) || (rc = dalloc(e, &G.nrec, cap)) ||
-        (rc = dalloc(e, &G.host_idx, cap)) || (rc = dalloc(e, &G.d_nfix, cap)))
-        return rc;
-    if (hipHostMalloc((void**)&G.res_h, cap * 8, hipHostMallocDefault) != hipSuccess) return e->fail(KWOK_ENOMEM, "node results");
-    G.ncap = cap;
+    if (n <= G.nodes.cap) return KWOK_OK;
+    G.res_h.release();
+    if (int rc = G.nodes.reserve(e, n)) return rc;
+    if (hipHostMalloc((void**)&G.res_h.p, G.nodes.cap * 8, hipHostMallocDefault) != hipSuccess) {
+        G.nodes.release();
+        return e->fail(KWOK_ENOMEM, "node results");
+    }
     return KWOK_OK;
 }
 
@@ -2248,7 +2187,7 @@ int ingest_pods_impl(kwok_engine* e, const void* recs, int packed, size_t n, con
         int8_t* m8 = out_status8 ? (int8_t*)host_mapped(out_status8 + lo, I.n) : nullptr;
         uint32_t* mr = out_released ? (uint32_t*)host_mapped(out_released + lo, (size_t)I.n * 4) : nullptr;
         if (packed == 2) {  // the chunk's creates' handles at their ordinals (copied back at the batch's end)
-            launch_ingest_new_handles(I, new_dst, (uint32_t)std::min<size_t>(new_cap, new_map ? new_cap : G.cap), rs);
+            launch_ingest_new_handles(I, new_dst, (uint32_t)std::min<size_t>(new_cap, new_map ? new_cap : G.recs.cap), rs);
             HIPCHK(e, hipGetLastError());
         }
         const bool mapped = e->results_kernel && (!out_handles || mh) && (!out_status || ms) && (!out_status8 || m8) &&
@@ -2497,33 +2436,16 @@ int json_reserve(kwok_engine* e, size_t n) {
     if (!J.cfg) {
         int rc = 0;
         if ((rc = dalloc(e, &J.cfg, 1)) || (rc = dalloc(e, &J.n_host, 1))) return rc;
-        if (hipHostMalloc((void**)&J.cfg_h, sizeof(JsonCfg), hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc((void**)&J.n_host_h, sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
+        if (hipHostMalloc((void**)&J.cfg_h.p, sizeof(JsonCfg), hipHostMallocDefault) != hipSuccess ||
+            hipHostMalloc((void**)&J.n_host_h.p, sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
             return e->fail(KWOK_ENOMEM, "GPU codec staging");
     }
-    if (n > J.cap) {
-        void* ptrs[] = {J.off, J.len, J.op, J.handle, J.side, J.host_list, J.fix_ev, J.fix_side};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-        J.off = nullptr, J.len = nullptr, J.op = nullptr, J.handle = nullptr, J.side = nullptr;
-        J.host_list = nullptr, J.fix_ev = nullptr, J.fix_side = nullptr;
-        J.cap = 0;
-        const size_t cap = std::max<size_t>(n + n / 4, 4096);
-        int rc = 0;
-        if ((rc = dalloc(e, &J.off, cap)) || (rc = dalloc(e, &J.len, cap)) || (rc = dalloc(e, &J.op, cap)) ||
-            (rc = dalloc(e, &J.handle, cap)) || (rc = dalloc(e, &J.side, cap)) || (rc = dalloc(e, &J.host_list, cap)) ||
-            (rc = dalloc(e, &J.fix_ev, cap)) || (rc = dalloc(e, &J.fix_side, cap)))
-            return rc;
-        J.cap = cap;
-    }
+    if (int rc = J.docs.reserve(e, n)) return rc;
     if (J.tab_dirty) {  // the spec table: open addressing at <= 50% load, rebuilt from spec_keys
         uint32_t slots = 1024;
         while (slots < 2 * e->spec_keys.size() + 2) slots <<= 1;
         if (slots - 1 != J.tab_mask || !J.tab_key) {
-            if (J.tab_key) (void)hipFree(J.tab_key);
-            if (J.tab_id) (void)hipFree(J.tab_id);
-            if (J.tab_canon) (void)hipFree(J.tab_canon);
-            J.tab_key = nullptr, J.tab_id = nullptr, J.tab_canon = nullptr;
+            dfree(J.tab_key), dfree(J.tab_id), dfree(J.tab_canon);
             int rc = 0;
             if ((rc = dalloc(e, &J.tab_key, slots)) || (rc = dalloc(e, &J.tab_id, slots)) ||
                 (rc = dalloc(e, &J.tab_canon, slots)))
@@ -2545,13 +2467,7 @@ int json_reserve(kwok_engine* e, size_t n) {
             cref[h] = uint2{(uint32_t)canon.size(), (uint32_t)c.size()};
             canon += c;
         }
-        if (canon.size() + 16 > J.canon_cap) {
-            if (J.canon) (void)hipFree(J.canon);
-            J.canon = nullptr, J.canon_cap = 0;
-            const size_t cap = std::max<size_t>(2 * canon.size() + 16, 4096);
-            if (int rc = dalloc(e, &J.canon, cap)) return rc;
-            J.canon_cap = cap;
-        }
+        if (int rc = J.canon_bytes.reserve(e, canon.size() + 16, 2 * canon.size() + 16)) return rc;
         HIPCHK(e, hipMemcpyAsync(J.tab_key, key.data(), slots * 8, hipMemcpyHostToDevice, e->st));
         HIPCHK(e, hipMemcpyAsync(J.tab_id, id.data(), slots * 4, hipMemcpyHostToDevice, e->st));
         HIPCHK(e, hipMemcpyAsync(J.tab_canon, cref.data(), slots * sizeof(uint2), hipMemcpyHostToDevice, e->st));
@@ -2635,7 +2551,7 @@ int json_decode(kwok_engine* e, const kwok_codec* c, const char* arena, size_t a
         A.tab_canon = J.tab_canon;
         A.key_mask = spec_key_mask();
         A.canon = J.canon;
-        A.ev = static_cast<kwok_pod_event*>(G.d_ev) + d0;
+        A.ev = static_cast<kwok_pod_event*>(G.d_ev.p) + d0;
         A.side = J.side + d0;
         A.host_list = J.host_list;
         A.n_host = J.n_host;
@@ -2672,7 +2588,7 @@ int json_complete(kwok_engine* e, const kwok_codec* c, const char* arena, size_t
     std::vector<uint32_t> list(nh);
     std::vector<kwok_pod_event> ev(nh);
     std::vector<JsonPodSide> side(nh);
-    launch_json_gather(static_cast<const kwok_pod_event*>(G.d_ev), J.side, J.host_list, nh, J.fix_ev, J.fix_side, st);
+    launch_json_gather(static_cast<const kwok_pod_event*>(G.d_ev.p), J.side, J.host_list, nh, J.fix_ev, J.fix_side, st);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipMemcpyAsync(list.data(), J.host_list, (size_t)nh * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipMemcpyAsync(ev.data(), J.fix_ev, (size_t)nh * sizeof(kwok_pod_event), hipMemcpyDeviceToHost, st));
@@ -2733,7 +2649,7 @@ int json_complete(kwok_engine* e, const kwok_codec* c, const char* arena, size_t
         s.status = rc;
     }
     HIPCHK(e, hipMemcpyAsync(J.fix_ev, ev.data(), (size_t)nh * sizeof(kwok_pod_event), hipMemcpyHostToDevice, st));
-    launch_json_scatter(static_cast<kwok_pod_event*>(G.d_ev), J.fix_ev, J.host_list, nh, st);
+    launch_json_scatter(static_cast<kwok_pod_event*>(G.d_ev.p), J.fix_ev, J.host_list, nh, st);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipStreamSynchronize(st));
     if (sides_out) *sides_out = std::move(side);
@@ -2776,14 +2692,7 @@ int json_nodes_decode(kwok_engine* e, const kwok_codec* c, const char* arena, si
     if ((rc = json_reserve(e, n))) return rc;
     auto& G = e->ing;
     auto& J = e->json;
-    if (n > J.ncap) {
-        if (J.nstat) (void)hipFree(J.nstat);
-        if (J.nev_fix) (void)hipFree(J.nev_fix);
-        J.nstat = nullptr, J.nev_fix = nullptr, J.ncap = 0;
-        const size_t cap = std::max<size_t>(n + n / 4, 4096);
-        if ((rc = dalloc(e, &J.nstat, cap)) || (rc = dalloc(e, &J.nev_fix, cap))) return rc;
-        J.ncap = cap;
-    }
+    if ((rc = J.node_docs.reserve(e, n))) return rc;
     hipStream_t st = e->st, ps = G.pst;
     if ((rc = codec_export(c, J.cfg_h))) {  // (selectors beyond the device tables: every document to the host)
         if (rc != KWOK_EDOMAIN) return e->fail(rc, "%s", kwok_codec_last_error());
@@ -3050,41 +2959,26 @@ static int watch_reserve(kwok_engine* e, size_t len) {
     auto& Wt = e->watch;
     if (!Wt.counts) {
         if (int rc = dalloc(e, &Wt.counts, 2)) return rc;
-        if (hipHostMalloc((void**)&Wt.counts_h, 2 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
+        if (hipHostMalloc((void**)&Wt.counts_h.p, 2 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
             return e->fail(KWOK_ENOMEM, "watch framer staging");
     }
     const size_t need = ((len + 15) & ~(size_t)15) + 16;  // (the readers take whole 16-byte windows)
-    if (need > Wt.cap) {
-        if (Wt.stream) (void)hipFree(Wt.stream);
-        Wt.stream = nullptr, Wt.cap = 0;
-        const size_t cap = std::max<size_t>(need + need / 4, 1 << 16);
-        if (int rc = dalloc(e, &Wt.stream, cap)) return rc;
-        Wt.cap = cap;
-    }
-    const size_t tiles = (len + KWOK_WATCH_TILE_BYTES - 1) / KWOK_WATCH_TILE_BYTES;
-    if (tiles > Wt.tile_cap) {
-        if (Wt.tile_cnt) (void)hipFree(Wt.tile_cnt);
-        if (Wt.tile_base) (void)hipFree(Wt.tile_base);
-        Wt.tile_cnt = Wt.tile_base = nullptr, Wt.tile_cap = 0;
-        const size_t cap = std::max<size_t>(tiles + tiles / 4, 1024);
-        int rc = 0;
-        if ((rc = dalloc(e, &Wt.tile_cnt, cap)) || (rc = dalloc(e, &Wt.tile_base, cap))) return rc;
-        Wt.tile_cap = cap;
-    }
+    if (int rc = Wt.bytes.reserve(e, need)) return rc;
+    return Wt.tiles.reserve(e, (len + KWOK_WATCH_TILE_BYTES - 1) / KWOK_WATCH_TILE_BYTES);
+}
+// a framed entry works on the frames of the last framing call only
+static int stream_resident(kwok_engine* e, uint64_t stream_id) {
+    if (!stream_id || stream_id != e->watch.id) return e->fail(KWOK_EINVAL, "stream_id is not the resident watch stream");
     return KWOK_OK;
 }
-static int watch_reserve_frames(kwok_engine* e, size_t n) {
-    auto& Wt = e->watch;
-    if (n <= Wt.fcap) return KWOK_OK;
-    void* ptrs[] = {Wt.ends, Wt.frames, Wt.host_list};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    Wt.ends = nullptr, Wt.frames = nullptr, Wt.host_list = nullptr, Wt.fcap = 0;
-    const size_t cap = std::max<size_t>(n + n / 4, 4096);
-    int rc = 0;
-    if ((rc = dalloc(e, &Wt.ends, cap)) || (rc = dalloc(e, &Wt.frames, cap)) || (rc = dalloc(e, &Wt.host_list, cap))) return rc;
-    Wt.fcap = cap;
-    return KWOK_OK;
+// The checks of the by-uid framed entry `who` before it touches anything: the engine in step with the
+// device, before and after the queued ticks are finished; the uid directory enabled; the stream resident.
+static int framed_enter(kwok_engine* e, const char* who, uint64_t stream_id) {
+    if (e->poisoned) return poisoned(e);
+    drain(e);
+    if (e->poisoned) return poisoned(e);
+    if (!e->uid.on) return e->fail(KWOK_EINVAL, "%s: the uid directory is not enabled", who);
+    return stream_resident(e, stream_id);
 }
 // the records of a framed batch from the host's copy of the frames: the object's
 // span and the op of the frame type; a record that names no ingestible frame gets
@@ -3093,7 +2987,7 @@ static int watch_reserve_frames(kwok_engine* e, size_t n) {
 static int framed_records(kwok_engine* e, uint64_t stream_id, const uint32_t* frame_idx, size_t n, std::vector<uint64_t>& off,
                    std::vector<uint32_t>& len, std::vector<uint8_t>& op) {
     auto& Wt = e->watch;
-    if (!stream_id || stream_id != Wt.id) return e->fail(KWOK_EINVAL, "stream_id is not the resident watch stream");
+    if (int rc = stream_resident(e, stream_id)) return rc;
     off.resize(n), len.resize(n), op.resize(n);
     for (size_t i = 0; i < n; i++) {
         const kwok_watch_frame* f = frame_idx[i] < Wt.frames_h.size() ? &Wt.frames_h[frame_idx[i]] : nullptr;
@@ -3105,11 +2999,6 @@ static int framed_records(kwok_engine* e, uint64_t stream_id, const uint32_t* fr
     }
     return KWOK_OK;
 }
-struct ArenaSrc {  // the ingest kernels read the batch's strings from the resident stream
-    kwok_engine* e;
-    ArenaSrc(kwok_engine* e_, const uint8_t* p) : e(e_) { e->ing.arena_src = p; }
-    ~ArenaSrc() { e->ing.arena_src = nullptr; }
-};
 }  // namespace
 
 int kwok_frame_watch_gpu(kwok_engine* e, const char* stream, size_t len, kwok_watch_frame* frames, size_t cap,
@@ -3130,20 +3019,9 @@ int kwok_frame_watch_gpu(kwok_engine* e, const char* stream, size_t len, kwok_wa
     const uint32_t tiles = (uint32_t)((len + KWOK_WATCH_TILE_BYTES - 1) / KWOK_WATCH_TILE_BYTES);
     const size_t padded = ((len + 15) & ~(size_t)15) + 16;
     // KWOK_INGEST_PROF: device-side stamps - upload | count + scan | emit | parse
-    hipEvent_t pe[5] = {};
     const auto t0 = clk::now();
-    if (e->iprof)
-        for (auto& x : pe) (void)hipEventCreate(&x);
-    auto stamp = [&](int k) {
-        if (pe[k]) (void)hipEventRecord(pe[k], st);
-    };
-    struct PeFree {
-        hipEvent_t* p;
-        ~PeFree() {
-            for (int k = 0; k < 5; k++)
-                if (p[k]) (void)hipEventDestroy(p[k]);
-        }
-    } pe_free{pe};
+    ProfEvents<5> pe(e->iprof, e->st);
+    auto stamp = [&](int k) { pe.stamp(k); };
     stamp(0);
     if (len) HIPCHK(e, hipMemcpyAsync(Wt.stream, stream, len, hipMemcpyHostToDevice, st));
     HIPCHK(e, hipMemsetAsync(Wt.stream + len, 0, padded - len, st));
@@ -3163,9 +3041,9 @@ int kwok_frame_watch_gpu(kwok_engine* e, const char* stream, size_t len, kwok_wa
         *stream_id = Wt.id = Wt.next_id++;
         return 0;
     }
-    if ((rc = watch_reserve_frames(e, n))) return rc;
-    const bool prof = pe[0] != nullptr;
-    if (prof) (void)hipEventRecord(pe[0], st);  // (re-used: the emit's start, after the host's wait for the count)
+    if ((rc = Wt.lines.reserve(e, n))) return rc;
+    const bool prof = pe.on();
+    stamp(0);  // (re-used: the emit's start, after the host's wait for the count)
     launch_frame_emit(Wt.stream, len, tiles, Wt.tile_base, Wt.ends, n, st);
     stamp(3);
     HIPCHK(e, hipMemsetAsync(Wt.counts + 1, 0, 4, st));
@@ -3202,10 +3080,7 @@ int kwok_frame_watch_gpu(kwok_engine* e, const char* stream, size_t len, kwok_wa
     Wt.stats[KWOK_WATCH_STAT_HOST_FRAMES] += nh;
     *stream_id = Wt.id = Wt.next_id++;
     if (prof) {
-        float cs = 0, em = 0, pa = 0;
-        (void)hipEventElapsedTime(&cs, pe[1], pe[2]);
-        (void)hipEventElapsedTime(&em, pe[0], pe[3]);
-        (void)hipEventElapsedTime(&pa, pe[3], pe[4]);
+        const float cs = pe.elapsed(1, 2), em = pe.elapsed(0, 3), pa = pe.elapsed(3, 4);
         fprintf(stderr, "[kwok watch] %zu bytes, %u frames (%u by the host): k_frame_count + k_frame_scan %.3f ms, "
                         "k_frame_emit %.3f ms, k_frame_parse %.3f ms; the call %.2f ms\n", len, n, nh, cs, em, pa,
                 ms_between(t0, clk::now()));
@@ -3234,7 +3109,7 @@ int kwok_ingest_pods_framed(kwok_engine* e, const kwok_codec* c, uint64_t stream
     if ((rc = json_complete(e, c, Wt.host, Wt.len, off.data(), len.data(), nh, op.data(), handle, nullptr, nullptr)))
         return rc;
     if (n_host) *n_host = nh;
-    ArenaSrc src(e, Wt.stream);
+    ScopedPtr<uint8_t> src(e->ing.arena_src, Wt.stream);  // the ingest kernels read the batch's strings from the resident stream
     return ingest_pods_impl(e, e->ing.d_ev, 0, n, nullptr, Wt.len, out_handles, out_status, nullptr, out_released, true);
 }
 
@@ -3249,7 +3124,7 @@ int kwok_ingest_nodes_framed(kwok_engine* e, const kwok_codec* c, uint64_t strea
     int rc = framed_records(e, stream_id, frame_idx, n, off, len, op);
     if (rc) return rc;
     Wt.stats[KWOK_WATCH_STAT_INGESTS]++;
-    ArenaSrc src(e, Wt.stream);
+    ScopedPtr<uint8_t> src(e->ing.arena_src, Wt.stream);  // the ingest kernels read the batch's strings from the resident stream
     return ingest_nodes_json_impl(e, c, Wt.host, Wt.len, off.data(), len.data(), op.data(), n, out_handles, out_status,
                                   n_host, Wt.stream);
 }
@@ -3267,27 +3142,10 @@ static int list_reserve(kwok_engine* e, size_t tiles) {
     auto& Wt = e->watch;
     if (!Wt.lc) {
         if (int rc = dalloc(e, &Wt.lc, (size_t)KWOK_LIST_COUNTERS)) return rc;
-        if (hipHostMalloc((void**)&Wt.lc_h, KWOK_LIST_COUNTERS * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
+        if (hipHostMalloc((void**)&Wt.lc_h.p, KWOK_LIST_COUNTERS * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
             return e->fail(KWOK_ENOMEM, "list framer staging");
     }
-    if (tiles > Wt.ltile_cap) {
-        if (Wt.ltile) (void)hipFree(Wt.ltile);
-        Wt.ltile = nullptr, Wt.ltile_cap = 0;
-        const size_t cap = std::max<size_t>(tiles + tiles / 4, 1024);
-        if (int rc = dalloc(e, &Wt.ltile, 8 * cap)) return rc;
-        Wt.ltile_cap = cap;
-    }
-    return KWOK_OK;
-}
-static int list_reserve_starts(kwok_engine* e, size_t n) {
-    auto& Wt = e->watch;
-    if (n <= Wt.scap) return KWOK_OK;
-    if (Wt.starts) (void)hipFree(Wt.starts);
-    Wt.starts = nullptr, Wt.scap = 0;
-    const size_t cap = std::max<size_t>(n + n / 4, 4096);
-    if (int rc = dalloc(e, &Wt.starts, cap)) return rc;
-    Wt.scap = cap;
-    return KWOK_OK;
+    return Wt.ltiles.reserve(e, tiles);
 }
 }  // namespace
 
@@ -3310,25 +3168,14 @@ int kwok_frame_list_gpu(kwok_engine* e, const char* body, size_t len, kwok_watch
     int rc = 0;
     if ((rc = watch_reserve(e, len)) || (rc = list_reserve(e, tiles))) return rc;
     const size_t padded = ((len + 15) & ~(size_t)15) + 16;
-    const size_t L = Wt.ltile_cap;
+    const size_t L = Wt.ltiles.cap;
     uint32_t *tq = Wt.ltile, *td0 = tq + L, *td1 = td0 + L, *qb = td1 + L, *db = qb + L, *ts = db + L, *te = ts + L;
     uint32_t *lc = Wt.lc, *lh = Wt.lc_h;
     // KWOK_INGEST_PROF: device-side stamps - upload | quotes + scans | count + scans | emit + range | parse
-    hipEvent_t pe[7] = {};
     const auto t0 = clk::now();
-    if (e->iprof)
-        for (auto& x : pe) (void)hipEventCreate(&x);
-    auto stamp = [&](int k) {
-        if (pe[k]) (void)hipEventRecord(pe[k], st);
-    };
-    struct PeFree {
-        hipEvent_t* p;
-        ~PeFree() {
-            for (int k = 0; k < 7; k++)
-                if (p[k]) (void)hipEventDestroy(p[k]);
-        }
-    } pe_free{pe};
-    const bool prof = pe[0] != nullptr;
+    ProfEvents<7> pe(e->iprof, e->st);
+    auto stamp = [&](int k) { pe.stamp(k); };
+    const bool prof = pe.on();
     float ms[4] = {0, 0, 0, 0};  // quotes, count, emit, parse
     uint32_t n = 0, nh = 0;
     auto report = [&](const char* how) {
@@ -3356,7 +3203,7 @@ int kwok_frame_list_gpu(kwok_engine* e, const char* body, size_t len, kwok_watch
     stamp(3);
     HIPCHK(e, hipMemcpyAsync(lh, lc, KWOK_LIST_COUNTERS * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipStreamSynchronize(st));
-    if (prof) (void)hipEventElapsedTime(&ms[0], pe[1], pe[2]), (void)hipEventElapsedTime(&ms[1], pe[2], pe[3]);
+    ms[0] = pe.elapsed(1, 2), ms[1] = pe.elapsed(2, 3);
     // a valid body ends outside every string and every bracket, and an array that its
     // root holds is closed once
     if ((lh[LC_QUOTES] & 1u) || lh[LC_DEPTH] != 0 || lh[LC_STARTS] != lh[LC_ENDS] || lh[LC_OPEN_N] != lh[LC_CLOSE_N] ||
@@ -3368,7 +3215,7 @@ int kwok_frame_list_gpu(kwok_engine* e, const char* body, size_t len, kwok_watch
     int env = 1;
     if (lh[LC_OPEN_N] == 1) {
         // the device's part goes on while the host reads the envelope
-        if ((rc = watch_reserve_frames(e, S)) || (rc = list_reserve_starts(e, S))) return rc;
+        if ((rc = Wt.lines.reserve(e, S)) || (rc = Wt.cands.reserve(e, S))) return rc;
         stamp(6);  // (the emit's start, after the host's wait for the counts)
         launch_list_emit(Wt.stream, len, tiles, qb, db, ts, te, Wt.starts, Wt.ends, S, st);
         launch_list_range(Wt.starts, S, open, close, lc, st);
@@ -3377,7 +3224,7 @@ int kwok_frame_list_gpu(kwok_engine* e, const char* body, size_t len, kwok_watch
         HIPCHK(e, hipMemcpyAsync(lh + LC_R0, lc + LC_R0, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         env = list_envelope(body, len, open, close, info);
         HIPCHK(e, hipStreamSynchronize(st));
-        if (prof) (void)hipEventElapsedTime(&ms[2], pe[6], pe[4]);
+        ms[2] = pe.elapsed(6, 4);
         if (env < 0) {
             report("a bad envelope");
             return e->fail(KWOK_EINVAL, "kwok_frame_list_gpu: the body is not a JSON object");
@@ -3392,7 +3239,7 @@ int kwok_frame_list_gpu(kwok_engine* e, const char* body, size_t len, kwok_watch
         n = rc ? 0u : (uint32_t)nf;
         report("the body framed by the host");
         if (rc) return e->fail(KWOK_EINVAL, "kwok_frame_list_gpu: %s", kwok_codec_last_error());
-        if ((rc = watch_reserve_frames(e, nf))) return rc;
+        if ((rc = Wt.lines.reserve(e, nf))) return rc;
         Wt.frames_h.assign(tmp.begin(), tmp.begin() + nf);
         if (nf) {
             HIPCHK(e, hipMemcpyAsync(Wt.frames, Wt.frames_h.data(), nf * sizeof(kwok_watch_frame), hipMemcpyHostToDevice, st));
@@ -3425,7 +3272,7 @@ int kwok_frame_list_gpu(kwok_engine* e, const char* body, size_t len, kwok_watch
     if (n) HIPCHK(e, hipMemcpyAsync(Wt.frames_h.data(), Wt.frames, (size_t)n * sizeof(kwok_watch_frame), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipMemcpyAsync(lh + LC_BAD, lc + LC_BAD, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipStreamSynchronize(st));
-    if (prof && n) (void)hipEventElapsedTime(&ms[3], pe[4], pe[5]);
+    if (n) ms[3] = pe.elapsed(4, 5);
     if (lh[LC_BAD]) {
         Wt.frames_h.clear();
         return invalid("an item or the text between items");
@@ -3485,12 +3332,12 @@ int kwok_resync_begin(kwok_engine* e, int kind) {
     if (!R.ctr) {
         if (int rc = dalloc(e, &R.ctr, 1)) return rc;
         if (int rc = dalloc(e, &R.total, 1)) return rc;
-        if (hipHostMalloc((void**)&R.ctr_h, sizeof(ResyncCounters), hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc((void**)&R.total_h, sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
+        if (hipHostMalloc((void**)&R.ctr_h.p, sizeof(ResyncCounters), hipHostMallocDefault) != hipSuccess ||
+            hipHostMalloc((void**)&R.total_h.p, sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
             return e->fail(KWOK_ENOMEM, "resync staging");
         memset(R.ctr_h, 0, sizeof(ResyncCounters));
     }
-    uint8_t*& seen = kind == KWOK_KIND_PODS ? R.pod_seen : R.node_seen;
+    DevArr<uint8_t>& seen = kind == KWOK_KIND_PODS ? R.pod_seen : R.node_seen;
     const size_t bytes = kind == KWOK_KIND_PODS ? e->PLa : e->NLa;
     if (!seen) {  // (zeroed by the allocation)
         if (int rc = dalloc(e, &seen, bytes)) return rc;
@@ -3517,13 +3364,7 @@ int kwok_resync_mark(kwok_engine* e, int kind, const int32_t* handles, size_t n,
     drain(e);  // (a handle is judged against the state after every submitted tick)
     if (e->poisoned) return poisoned(e);
     if (!n) return KWOK_OK;
-    if (n > R.mark_cap) {
-        if (R.d_mark) (void)hipFree(R.d_mark);
-        R.d_mark = nullptr, R.mark_cap = 0;
-        const size_t cap = std::max<size_t>(n + n / 4, 4096);
-        if (int rc = dalloc(e, &R.d_mark, cap)) return rc;
-        R.mark_cap = cap;
-    }
+    if (int rc = R.marks.reserve(e, n)) return rc;
     hipStream_t st = e->st;
     HIPCHK(e, hipMemcpyAsync(R.d_mark, handles, n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(e, hipMemsetAsync(&R.ctr->bad, 0, sizeof(R.ctr->bad), st));
@@ -3550,30 +3391,11 @@ int kwok_resync_sweep(kwok_engine* e, int kind, int32_t* out_handles, size_t cap
     hipStream_t st = e->st;
     const auto t0 = clk::now();
     // KWOK_INGEST_PROF: device-side stamps around count + scan and around emit
-    hipEvent_t pev[4] = {};
-    if (e->iprof)
-        for (auto& x : pev) (void)hipEventCreate(&x);
-    struct PevGuard {
-        hipEvent_t* p;
-        ~PevGuard() {
-            for (int k = 0; k < 4; k++)
-                if (p[k]) (void)hipEventDestroy(p[k]);
-        }
-    } pev_guard{pev};
-    auto stamp = [&](int k) {
-        if (pev[k]) (void)hipEventRecord(pev[k], st);
-    };
+    ProfEvents<4> pev(e->iprof, e->st);
+    auto stamp = [&](int k) { pev.stamp(k); };
     // pass 1: the unmarked live objects per tile, their exclusive prefixes and the total
     const uint32_t tiles = sweep_tiles(e->S, pods);
-    if (tiles > R.tile_cap) {
-        if (R.tile_cnt) (void)hipFree(R.tile_cnt);
-        if (R.tile_base) (void)hipFree(R.tile_base);
-        R.tile_cnt = R.tile_base = nullptr, R.tile_cap = 0;
-        const size_t tc = std::max<size_t>(tiles + tiles / 4, 1024);
-        int rc = 0;
-        if ((rc = dalloc(e, &R.tile_cnt, tc)) || (rc = dalloc(e, &R.tile_base, tc))) return rc;
-        R.tile_cap = tc;
-    }
+    if (int rc = R.tiles.reserve(e, tiles)) return rc;
     stamp(0);
     launch_sweep_count(e->S, pods, seen, R.tile_cnt, st);
     launch_frame_scan(R.tile_cnt, tiles, R.tile_base, R.total, st);
@@ -3587,22 +3409,13 @@ int kwok_resync_sweep(kwok_engine* e, int kind, int32_t* out_handles, size_t cap
     R.open[kind] = false;  // the sweep closes the session (its DELETE records mark nothing)
     if (!n) {
         if (e->iprof) {
-            float cs = 0;
-            (void)hipEventElapsedTime(&cs, pev[0], pev[1]);
+            const float cs = pev.elapsed(0, 1);
             fprintf(stderr, "[kwok resync] %s: %u tiles, 0 swept: k_sweep_count + k_frame_scan %.3f ms; the call %.3f ms\n",
                     pods ? "pods" : "nodes", tiles, cs, ms_between(t0, clk::now()));
         }
         return KWOK_OK;
     }
-    if (n > R.out_cap) {
-        if (R.d_handles) (void)hipFree(R.d_handles);
-        if (R.d_nodes) (void)hipFree(R.d_nodes);
-        R.d_handles = R.d_nodes = nullptr, R.out_cap = 0;
-        const size_t oc = std::max<size_t>(n + n / 4, 4096);
-        int rc = 0;
-        if ((rc = dalloc(e, &R.d_handles, oc)) || (rc = dalloc(e, &R.d_nodes, oc))) return rc;
-        R.out_cap = oc;
-    }
+    if (int rc = R.swept.reserve(e, n)) return rc;
     // pass 2: the DELETE records into the ingest's own record buffer, in slot order; then the ingest's chain
     // over them, resident (no record or name crosses the link)
     int rc = pods ? ingest_reserve(e, n, 0) : node_reserve(e, n, 0);
@@ -3627,7 +3440,7 @@ int kwok_resync_sweep(kwok_engine* e, int kind, int32_t* out_handles, size_t cap
         const std::vector<kwok_node_event> hrec;
         const std::vector<std::string> hbuf;
         const NodeJsonCtx ctx{nullptr, &hdoc, &hrec, &hbuf};
-        ArenaSrc names(e, e->S.node_name);  // the records' name spans index the directory's own names
+        ScopedPtr<uint8_t> names(e->ing.arena_src, e->S.node_name);  // the records' name spans index the directory's own names
         rc = ingest_nodes_impl(e, nullptr, n, nullptr, (size_t)e->NL * NAME_STRIDE, nullptr, nullptr, &ctx);
     }
     if (rc < 0) return rc;
@@ -3641,9 +3454,7 @@ int kwok_resync_sweep(kwok_engine* e, int kind, int32_t* out_handles, size_t cap
     R.stats[pods ? KWOK_RESYNC_STAT_SWEPT_PODS : KWOK_RESYNC_STAT_SWEPT_NODES] += n;
     R.stats[KWOK_RESYNC_STAT_RELEASED] += released;
     if (e->iprof) {
-        float cs = 0, em = 0;
-        (void)hipEventElapsedTime(&cs, pev[0], pev[1]);
-        (void)hipEventElapsedTime(&em, pev[2], pev[3]);
+        const float cs = pev.elapsed(0, 1), em = pev.elapsed(2, 3);
         fprintf(stderr, "[kwok resync] %s: %u tiles, %u swept (%llu addresses put back): k_sweep_count + k_frame_scan %.3f ms, "
                         "k_sweep_emit %.3f ms, apply chain + results %.3f ms; the call %.3f ms\n", pods ? "pods" : "nodes", tiles,
                 n, (unsigned long long)released, cs, em, ms_between(t2, clk::now()), ms_between(t0, clk::now()));
@@ -3729,20 +3540,7 @@ int uid_upload(kwok_engine* e, const int32_t* handles, const char* arena, const 
     for (size_t i = 0; i < n; i++)  // (the bytes the spans name; a span past 2^40 is the caller's error)
         if (len[i] && len[i] <= KWOK_UID_MAX && off[i] < (1ull << 40)) al = std::max<uint64_t>(al, off[i] + len[i]);
     int rc = 0;
-    if (n > U.qcap) {
-        dfree(U.q_h), dfree(U.q_off), dfree(U.q_len);
-        U.qcap = 0;
-        const size_t cap = std::max<size_t>(n + n / 4, 4096);
-        if ((rc = dalloc(e, &U.q_h, cap)) || (rc = dalloc(e, &U.q_off, cap)) || (rc = dalloc(e, &U.q_len, cap))) return rc;
-        U.qcap = cap;
-    }
-    if (al + 1 > U.acap) {
-        dfree(U.q_arena);
-        U.acap = 0;
-        const size_t cap = std::max<size_t>(al + al / 4 + 1, 1 << 16);
-        if ((rc = dalloc(e, &U.q_arena, cap))) return rc;
-        U.acap = cap;
-    }
+    if ((rc = U.spans.reserve(e, n)) || (rc = U.arena.reserve(e, al + 1, grown(al) + 1))) return rc;
     hipStream_t st = e->st;
     if (handles) HIPCHK(e, hipMemcpyAsync(U.q_h, handles, n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(e, hipMemcpyAsync(U.q_off, off, n * 8, hipMemcpyHostToDevice, st));
@@ -3751,16 +3549,6 @@ int uid_upload(kwok_engine* e, const int32_t* handles, const char* arena, const 
     *arena_len = al;
     return KWOK_OK;
 }
-struct NoteSrc {  // the ingest notes the by-uid batch's creates with their uids
-    kwok_engine* e;
-    NoteSrc(kwok_engine* e_, const UidNote* n) : e(e_) { e->uid.note = n; }
-    ~NoteSrc() { e->uid.note = nullptr; }
-};
-struct RefNoteSrc {  // ... and, with the reference directory, with their frames' namespaces and names
-    kwok_engine* e;
-    RefNoteSrc(kwok_engine* e_, const RefNote* n) : e(e_) { e->refs.note = n; }
-    ~RefNoteSrc() { e->refs.note = nullptr; }
-};
 }  // namespace
 
 int kwok_uid_dir_enable(kwok_engine* e) {
@@ -3779,8 +3567,8 @@ int kwok_uid_dir_enable(kwok_engine* e) {
     int rc = 0;  // (dalloc zeroes: no uid known, an empty table)
     if (!U.ctr) {
         if ((rc = dalloc(e, &U.ctr, 1)) || (rc = dalloc(e, &U.run, 1))) return rc;
-        if (hipHostMalloc((void**)&U.ctr_h, sizeof(UidCounters), hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc((void**)&U.run_h, sizeof(UidRun), hipHostMallocDefault) != hipSuccess)
+        if (hipHostMalloc((void**)&U.ctr_h.p, sizeof(UidCounters), hipHostMallocDefault) != hipSuccess ||
+            hipHostMalloc((void**)&U.run_h.p, sizeof(UidRun), hipHostMallocDefault) != hipSuccess)
             return e->fail(KWOK_ENOMEM, "uid directory staging");
         memset(U.ctr_h, 0, sizeof(UidCounters));
     }
@@ -3865,54 +3653,24 @@ namespace {
 int pods_framed_uid_impl(kwok_engine* e, const kwok_codec* c, uint64_t stream_id, const uint32_t* frame_idx,
                          const uint32_t* dev_idx, size_t n, int32_t* out_handles, int32_t* out_status, uint32_t* out_released,
                          size_t* n_host, size_t* n_runs) {
-    if (e->poisoned) return poisoned(e);
-    drain(e);
-    if (e->poisoned) return poisoned(e);
+    if (int rc = framed_enter(e, "kwok_ingest_pods_framed_uid", stream_id)) return rc;
     auto& U = e->uid;
     auto& Wt = e->watch;
     auto& J = e->json;
     auto& G = e->ing;
-    if (!U.on) return e->fail(KWOK_EINVAL, "kwok_ingest_pods_framed_uid: the uid directory is not enabled");
-    if (!stream_id || stream_id != Wt.id) return e->fail(KWOK_EINVAL, "stream_id is not the resident watch stream");
     if (!n) return 0;
     hipStream_t st = e->st;
     const auto t0 = clk::now();
     int rc = 0;
     // the per-record buffers of the call, the decode's and the ingest's sized for the whole batch
     // (a run is a prefix of a range: no later reserve moves them)
-    if (n > U.cap) {
-        dfree(U.fidx), dfree(U.uoff), dfree(U.res_rel), dfree(U.ulen), dfree(U.cls), dfree(U.hash), dfree(U.res_h), dfree(U.res_st);
-        U.cap = 0;
-        const size_t cap = std::max<size_t>(n + n / 4, 4096);
-        if ((rc = dalloc(e, &U.fidx, cap)) || (rc = dalloc(e, &U.uoff, cap)) || (rc = dalloc(e, &U.res_rel, cap)) ||
-            (rc = dalloc(e, &U.ulen, cap)) || (rc = dalloc(e, &U.cls, cap)) || (rc = dalloc(e, &U.hash, cap)) ||
-            (rc = dalloc(e, &U.res_h, cap)) || (rc = dalloc(e, &U.res_st, cap)))
-            return rc;
-        U.cap = cap;
-    }
-    size_t ccap = 64;
-    while (ccap < 2 * n) ccap <<= 1;
-    if (ccap > U.claim_cap) {
-        dfree(U.claim);
-        U.claim_cap = 0;
-        if ((rc = dalloc(e, &U.claim, ccap))) return rc;
-        U.claim_cap = ccap;
-    }
+    if ((rc = U.recs.reserve(e, n)) || (rc = U.claims.reserve(e, claim_size(n), claim_size(n)))) return rc;
     if ((rc = ingest_reserve(e, n, 0)) || (rc = json_reserve(e, n))) return rc;
     if (dev_idx) HIPCHK(e, hipMemcpyAsync(U.fidx, dev_idx, n * 4, hipMemcpyDeviceToDevice, st));
     else HIPCHK(e, hipMemcpyAsync(U.fidx, frame_idx, n * 4, hipMemcpyHostToDevice, st));
     std::vector<uint32_t> idx_h;  // (dev_idx: fetched for the documents the host completes)
     // KWOK_INGEST_PROF: device-side stamps around k_uid_resolve and around k_uid_claim + k_uid_cut
-    hipEvent_t pev[3] = {};
-    if (e->iprof)
-        for (auto& x : pev) (void)hipEventCreate(&x);
-    struct PevGuard {
-        hipEvent_t* p;
-        ~PevGuard() {
-            for (int k = 0; k < 3; k++)
-                if (p[k]) (void)hipEventDestroy(p[k]);
-        }
-    } pev_guard{pev};
+    ProfEvents<3> pev(e->iprof, e->st);
     float ms_resolve = 0, ms_cut = 0, ms_note = 0;
     UidBatch B{};
     B.stream = Wt.stream;
@@ -3930,27 +3688,21 @@ int pods_framed_uid_impl(kwok_engine* e, const kwok_codec* c, uint64_t stream_id
     for (size_t lo = 0; lo < n;) {
         const size_t range = n - lo;
         if ((rc = uid_ensure(e, 0))) return rc;  // (the table sized for the slots before it is probed)
-        size_t cm = 64;
-        while (cm < 2 * range) cm <<= 1;
+        const size_t cm = claim_size(range);
         B.lo = (uint32_t)lo;
         B.claim_mask = (uint32_t)(cm - 1);
         U.run_h->first_cut = ~0u, U.run_h->n_sent = 0, U.run_h->n_new = 0, U.run_h->pad = 0;
         HIPCHK(e, hipMemcpyAsync(U.run, U.run_h, sizeof(UidRun), hipMemcpyHostToDevice, st));
         HIPCHK(e, hipMemsetAsync(U.claim, 0xFF, cm * 4, st));
-        if (pev[0]) (void)hipEventRecord(pev[0], st);
+        pev.stamp(0);
         launch_uid_resolve(e->S, U.dir(), B, st);
-        if (pev[1]) (void)hipEventRecord(pev[1], st);
+        pev.stamp(1);
         launch_uid_cut(B, st);
-        if (pev[2]) (void)hipEventRecord(pev[2], st);
+        pev.stamp(2);
         HIPCHK(e, hipGetLastError());
         HIPCHK(e, hipMemcpyAsync(U.run_h, U.run, sizeof(UidRun), hipMemcpyDeviceToHost, st));
         HIPCHK(e, hipStreamSynchronize(st));
-        if (pev[0]) {
-            float a = 0, b = 0;
-            (void)hipEventElapsedTime(&a, pev[0], pev[1]);
-            (void)hipEventElapsedTime(&b, pev[1], pev[2]);
-            ms_resolve += a, ms_cut += b;
-        }
+        ms_resolve += pev.elapsed(0, 1), ms_cut += pev.elapsed(1, 2);
         const size_t cut = std::min<size_t>(U.run_h->first_cut, n);
         if (cut <= lo) return e->fail(KWOK_EDEVICE, "uid directory: a run of no records at %zu", lo);
         const size_t m = cut - lo;
@@ -3984,10 +3736,10 @@ int pods_framed_uid_impl(kwok_engine* e, const kwok_codec* c, uint64_t stream_id
                 host_docs += nh;
             }
             const UidNote N{Wt.stream, U.uoff + lo, U.ulen + lo, U.hash + lo, U.cls + lo};
-            NoteSrc note(e, &N);
+            ScopedPtr<UidNote> note(e->uid.note, &N);  // the ingest notes the run's creates with their uids
             const RefNote RN{Wt.stream, Wt.len, Wt.frames, B.n_frames, U.fidx + lo, U.cls + lo};
-            RefNoteSrc ref_note(e, &RN);
-            ArenaSrc src(e, Wt.stream);
+            ScopedPtr<RefNote> ref_note(e->refs.note, &RN);  // ... and, with the reference directory, with their names
+            ScopedPtr<uint8_t> src(e->ing.arena_src, Wt.stream);
             rc = ingest_pods_impl(e, G.d_ev, 0, m, nullptr, Wt.len, nullptr, nullptr, nullptr, nullptr, true);
             for (size_t q = 0; q + 1 < U.note_ev.size(); q += 2) {  // (the batch is synchronised, or failed)
                 float ms = 0;
@@ -4082,8 +3834,8 @@ int echo_rebuild(kwok_engine* e, size_t tab_cap) {
     launch_echo_rebuild(from, to, used, st);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipStreamSynchronize(st));
-    dfree(E.tab), dfree(E.pool);
-    E.tab = tab, E.tab_cap = tab_cap, E.pool = pool, E.pool_cap = pool_cap;
+    E.tab.reset(tab), E.pool.reset(pool);
+    E.tab_cap = tab_cap, E.pool_cap = pool_cap;
     E.rebuilds++;
     if ((rc = echo_read(e, false))) return rc;
     if (E.ctr_h->used != E.ctr_h->live) {
@@ -4114,31 +3866,8 @@ int echo_ensure(kwok_engine* e, size_t incoming) {
 int echo_reserve(kwok_engine* e, size_t n) {
     auto& E = e->echo;
     int rc = 0;
-    if (n > E.cap) {
-        dfree(E.uoff), dfree(E.roff), dfree(E.own), dfree(E.cnt), dfree(E.fill), dfree(E.lbase), dfree(E.list), dfree(E.fidx);
-        dfree(E.bsum), dfree(E.kidx), dfree(E.kpos), dfree(E.q_len), dfree(E.res_rel), dfree(E.ulen), dfree(E.rlen);
-        dfree(E.kind), dfree(E.res), dfree(E.hash), dfree(E.q_off), dfree(E.hdrop), dfree(E.res_h), dfree(E.res_st);
-        E.cap = 0;
-        const size_t cap = std::max<size_t>(n + n / 4, 4096);
-        if ((rc = dalloc(e, &E.uoff, cap)) || (rc = dalloc(e, &E.roff, cap)) || (rc = dalloc(e, &E.own, cap)) ||
-            (rc = dalloc(e, &E.cnt, cap)) || (rc = dalloc(e, &E.fill, cap)) || (rc = dalloc(e, &E.lbase, cap)) ||
-            (rc = dalloc(e, &E.list, cap)) || (rc = dalloc(e, &E.fidx, cap)) || (rc = dalloc(e, &E.bsum, cap / 256 + 2)) ||
-            (rc = dalloc(e, &E.kidx, cap)) || (rc = dalloc(e, &E.kpos, cap)) || (rc = dalloc(e, &E.q_len, cap)) ||
-            (rc = dalloc(e, &E.res_rel, cap)) || (rc = dalloc(e, &E.ulen, cap)) || (rc = dalloc(e, &E.rlen, cap)) ||
-            (rc = dalloc(e, &E.kind, cap)) || (rc = dalloc(e, &E.res, cap)) || (rc = dalloc(e, &E.hash, cap)) ||
-            (rc = dalloc(e, &E.q_off, cap)) || (rc = dalloc(e, &E.hdrop, cap)) || (rc = dalloc(e, &E.res_h, cap)) ||
-            (rc = dalloc(e, &E.res_st, cap)))
-            return rc;
-        E.cap = cap;
-    }
-    size_t ccap = 64;
-    while (ccap < 2 * n) ccap <<= 1;
-    if (ccap > E.claim_cap) {
-        dfree(E.claim);
-        E.claim_cap = 0;
-        if ((rc = dalloc(e, &E.claim, ccap))) return rc;
-        E.claim_cap = ccap;
-    }
+    const size_t ccap = claim_size(n);
+    if ((rc = E.recs.reserve(e, n)) || (rc = E.claims.reserve(e, ccap, ccap))) return rc;
     hipStream_t st = e->st;
     HIPCHK(e, hipMemsetAsync(E.claim, 0xFF, ccap * 4, st));
     HIPCHK(e, hipMemsetAsync(E.cnt, 0, n * 4, st));
@@ -4148,12 +3877,10 @@ int echo_reserve(kwok_engine* e, size_t n) {
 }
 EchoBatch echo_batch(kwok_engine* e, const uint8_t* base, uint64_t base_len, size_t n) {
     auto& E = e->echo;
-    size_t ccap = 64;
-    while (ccap < 2 * n) ccap <<= 1;
     EchoBatch B{};
     B.base = base, B.base_len = base_len, B.n = (uint32_t)n;
     B.uoff = E.uoff, B.roff = E.roff, B.ulen = E.ulen, B.rlen = E.rlen, B.hash = E.hash, B.kind = E.kind, B.res = E.res;
-    B.claim = E.claim, B.claim_mask = (uint32_t)(ccap - 1);
+    B.claim = E.claim, B.claim_mask = (uint32_t)(claim_size(n) - 1);
     B.own = E.own, B.cnt = E.cnt, B.fill = E.fill, B.lbase = E.lbase, B.list = E.list;
     B.call = E.call;
     return B;
@@ -4169,22 +3896,7 @@ int echo_upload(kwok_engine* e, const uint8_t* op, const char* arena, const uint
     }
     if (al && !arena) return KWOK_EINVAL;
     int rc = 0;
-    if (n > E.scap) {
-        dfree(E.s_uoff), dfree(E.s_roff), dfree(E.s_ulen), dfree(E.s_rlen), dfree(E.s_op), dfree(E.s_status);
-        E.scap = 0;
-        const size_t cap = std::max<size_t>(n + n / 4, 4096);
-        if ((rc = dalloc(e, &E.s_uoff, cap)) || (rc = dalloc(e, &E.s_roff, cap)) || (rc = dalloc(e, &E.s_ulen, cap)) ||
-            (rc = dalloc(e, &E.s_rlen, cap)) || (rc = dalloc(e, &E.s_op, cap)) || (rc = dalloc(e, &E.s_status, cap)))
-            return rc;
-        E.scap = cap;
-    }
-    if (al + 1 > E.acap) {
-        dfree(E.arena);
-        E.acap = 0;
-        const size_t cap = std::max<size_t>(al + al / 4 + 1, 1 << 16);
-        if ((rc = dalloc(e, &E.arena, cap))) return rc;
-        E.acap = cap;
-    }
+    if ((rc = E.spans.reserve(e, n)) || (rc = E.bytes.reserve(e, al + 1, grown(al) + 1))) return rc;
     hipStream_t st = e->st;
     HIPCHK(e, hipMemcpyAsync(E.s_uoff, uid_off, n * 8, hipMemcpyHostToDevice, st));
     HIPCHK(e, hipMemcpyAsync(E.s_roff, rv_off, n * 8, hipMemcpyHostToDevice, st));
@@ -4216,26 +3928,18 @@ int echo_filter_frames(kwok_engine* e, const uint32_t* frame_idx, size_t n, Echo
     const EchoBatch B = echo_batch(e, Wt.stream, Wt.len, n);
     const EchoFrames F{Wt.frames, (uint32_t)Wt.frames_h.size(), E.fidx};
     const EchoKeep K{E.bsum, E.kidx, E.kpos, E.q_off, E.q_len};
-    hipEvent_t pev[2] = {};
-    if (e->iprof)
-        for (auto& x : pev) (void)hipEventCreate(&x);
-    if (pev[0]) (void)hipEventRecord(pev[0], st);
+    ProfEvents<2> pev(e->iprof, e->st);
+    pev.stamp(0);
     launch_echo_key_frames(B, F, st);
     launch_echo_group(B, st);
     launch_echo_decide(E.ledger(), B, st);
     launch_echo_keep(B, F, K, st);
-    if (pev[1]) (void)hipEventRecord(pev[1], st);
+    pev.stamp(1);
     HIPCHK(e, hipGetLastError());
-    rc = echo_read(e, true);
-    if (pev[0] && pev[1]) {
-        float ms = 0;
-        if (!rc && hipEventElapsedTime(&ms, pev[0], pev[1]) == hipSuccess)
-            fprintf(stderr, "[kwok echo] %zu frames, %u echoes, %u repeats: the echo kernels %.3f ms\n", n, E.call_h->n_drop,
-                    E.call_h->n_rep, ms);
-    }
-    for (auto& x : pev)
-        if (x) (void)hipEventDestroy(x);
-    if (rc) return rc;
+    if ((rc = echo_read(e, true))) return rc;
+    if (pev.on())
+        fprintf(stderr, "[kwok echo] %zu frames, %u echoes, %u repeats: the echo kernels %.3f ms\n", n, E.call_h->n_drop,
+                E.call_h->n_rep, pev.elapsed(0, 1));
     if (E.call_h->n_keep > n) return e->fail(KWOK_EDEVICE, "echo ledger: %u of %zu records kept", E.call_h->n_keep, n);
     *Bo = B, *Fo = F, *Ko = K;
     return KWOK_OK;
@@ -4256,8 +3960,8 @@ int kwok_echo_enable(kwok_engine* e) {
     int rc = 0;  // (dalloc zeroes: an empty table, no note)
     if (!E.ctr) {
         if ((rc = dalloc(e, &E.ctr, 1)) || (rc = dalloc(e, &E.call, 1))) return rc;
-        if (hipHostMalloc((void**)&E.ctr_h, sizeof(EchoCounters), hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc((void**)&E.call_h, sizeof(EchoCall), hipHostMallocDefault) != hipSuccess)
+        if (hipHostMalloc((void**)&E.ctr_h.p, sizeof(EchoCounters), hipHostMallocDefault) != hipSuccess ||
+            hipHostMalloc((void**)&E.call_h.p, sizeof(EchoCall), hipHostMallocDefault) != hipSuccess)
             return e->fail(KWOK_ENOMEM, "echo ledger staging");
         memset(E.ctr_h, 0, sizeof(EchoCounters));
         memset(E.call_h, 0, sizeof(EchoCall));
@@ -4337,7 +4041,7 @@ int kwok_ingest_pods_framed_echo(kwok_engine* e, const kwok_codec* c, uint64_t s
     auto& U = e->uid;
     auto& Wt = e->watch;
     if (!U.on) return e->fail(KWOK_EINVAL, "kwok_ingest_pods_framed_echo: the uid directory is not enabled");
-    if (!stream_id || stream_id != Wt.id) return e->fail(KWOK_EINVAL, "stream_id is not the resident watch stream");
+    if ((rc = stream_resident(e, stream_id))) return rc;
     if (!n) return 0;
     hipStream_t st = e->st;
     EchoBatch B{};
@@ -4377,8 +4081,7 @@ int kwok_ingest_nodes_framed_echo(kwok_engine* e, const kwok_codec* c, uint64_t 
     int rc = echo_enter(e, "kwok_ingest_nodes_framed_echo");
     if (rc) return rc;
     auto& E = e->echo;
-    auto& Wt = e->watch;
-    if (!stream_id || stream_id != Wt.id) return e->fail(KWOK_EINVAL, "stream_id is not the resident watch stream");
+    if ((rc = stream_resident(e, stream_id))) return rc;
     if (!n) return 0;
     hipStream_t st = e->st;
     EchoBatch B{};
@@ -4449,21 +4152,12 @@ int refs_query(kwok_engine* e, const char* who, const int32_t* handles, size_t f
     hipStream_t st = e->st;
     if (!n) return KWOK_OK;
     int rc = 0;
-    if (n > R.qcap) {
-        dfree(R.q_len), dfree(R.q_off), dfree(R.q_slot), dfree(R.q_refs);
-        R.qcap = 0;
-        const size_t cap = std::max<size_t>(n + n / 4, 4096);
-        if ((rc = dalloc(e, &R.q_len, cap)) || (rc = dalloc(e, &R.q_off, cap)) || (rc = dalloc(e, &R.q_slot, cap)) ||
-            (rc = dalloc(e, &R.q_refs, cap)))
-            return rc;
-        R.qcap = cap;
-    }
+    if ((rc = R.items.reserve(e, n))) return rc;
     const size_t tmp = refs_scan_bytes((uint32_t)n);
     if (tmp > R.tmp_bytes) {
-        if (R.q_tmp) (void)hipFree(R.q_tmp);
-        R.q_tmp = nullptr, R.tmp_bytes = 0;
+        R.q_tmp.release(), R.tmp_bytes = 0;
         const size_t want = tmp + tmp / 4 + 256;
-        if (hipMalloc(&R.q_tmp, want) != hipSuccess) return e->fail(KWOK_ENOMEM, "%s: scan storage", who);
+        if (hipMalloc(&R.q_tmp.p, want) != hipSuccess) return e->fail(KWOK_ENOMEM, "%s: scan storage", who);
         R.tmp_bytes = want;
     }
     RefQuery Q{};
@@ -4473,22 +4167,13 @@ int refs_query(kwok_engine* e, const char* who, const int32_t* handles, size_t f
     Q.len = R.q_len, Q.off = R.q_off, Q.refs = R.q_refs;
     // KWOK_INGEST_PROF: device-side stamps around k_refs_size, the scan and k_refs_gather
     const auto t0 = clk::now();
-    hipEvent_t pev[5] = {};
-    if (e->iprof)
-        for (auto& x : pev) (void)hipEventCreate(&x);
-    struct PevGuard {
-        hipEvent_t* p;
-        ~PevGuard() {
-            for (int k = 0; k < 5; k++)
-                if (p[k]) (void)hipEventDestroy(p[k]);
-        }
-    } pev_guard{pev};
-    if (pev[0]) (void)hipEventRecord(pev[0], st);
+    ProfEvents<5> pev(e->iprof, e->st);
+    pev.stamp(0);
     launch_refs_size(e->S, e->ref_dir(), Q, R.q_slot, st);
-    if (pev[1]) (void)hipEventRecord(pev[1], st);
+    pev.stamp(1);
     HIPCHK(e, hipGetLastError());
     if (launch_refs_scan(Q, R.q_tmp, R.tmp_bytes, st)) return e->fail(KWOK_EDEVICE, "%s: scan", who);
-    if (pev[2]) (void)hipEventRecord(pev[2], st);
+    pev.stamp(2);
     uint64_t tail[2] = {0, 0};  // the last item's offset and size: the total
     HIPCHK(e, hipMemcpyAsync(&tail[0], R.q_off + (n - 1), 8, hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipMemcpyAsync(&tail[1], R.q_len + (n - 1), 8, hipMemcpyDeviceToHost, st));
@@ -4497,26 +4182,17 @@ int refs_query(kwok_engine* e, const char* who, const int32_t* handles, size_t f
     if (blob_used) *blob_used = (size_t)total;
     if (total > blob_cap || (total && !blob))
         return e->fail(KWOK_EINVAL, "%s: blob_cap %zu < %llu", who, blob_cap, (unsigned long long)total);
-    if (total > R.blob_cap) {
-        dfree(R.q_blob);
-        R.blob_cap = 0;
-        const size_t cap = std::max<size_t>(total + total / 4, 1 << 16);
-        if ((rc = dalloc(e, &R.q_blob, cap))) return rc;
-        R.blob_cap = cap;
-    }
+    if ((rc = R.blob.reserve(e, total))) return rc;
     Q.blob = R.q_blob;
-    if (pev[3]) (void)hipEventRecord(pev[3], st);
+    pev.stamp(3);
     launch_refs_gather(e->S, e->ref_dir(), Q, R.q_slot, st);
-    if (pev[4]) (void)hipEventRecord(pev[4], st);
+    pev.stamp(4);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipMemcpyAsync(refs, R.q_refs, n * sizeof(kwok_ref), hipMemcpyDeviceToHost, st));
     if (total) HIPCHK(e, hipMemcpyAsync(blob, R.q_blob, total, hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipStreamSynchronize(st));
-    if (pev[4]) {
-        float ms_size = 0, ms_scan = 0, ms_gather = 0;
-        (void)hipEventElapsedTime(&ms_size, pev[0], pev[1]);
-        (void)hipEventElapsedTime(&ms_scan, pev[1], pev[2]);
-        (void)hipEventElapsedTime(&ms_gather, pev[3], pev[4]);
+    if (pev.on()) {
+        const float ms_size = pev.elapsed(0, 1), ms_scan = pev.elapsed(1, 2), ms_gather = pev.elapsed(3, 4);
         fprintf(stderr, "[kwok refs] %s: %zu %s, %llu blob bytes: k_refs_size %.3f ms, scan %.3f ms, k_refs_gather %.3f ms; "
                         "the call %.2f ms\n", who, n, pods ? "pods" : "nodes", (unsigned long long)total, ms_size, ms_scan, ms_gather,
                 ms_between(t0, clk::now()));
@@ -4535,7 +4211,7 @@ int kwok_refs_enable(kwok_engine* e) {
     if (rc) return rc;
     if (!R.ctr) {
         if ((rc = dalloc(e, &R.ctr, 1))) return rc;
-        if (hipHostMalloc((void**)&R.ctr_h, sizeof(RefCounters), hipHostMallocDefault) != hipSuccess)
+        if (hipHostMalloc((void**)&R.ctr_h.p, sizeof(RefCounters), hipHostMallocDefault) != hipSuccess)
             return e->fail(KWOK_ENOMEM, "reference directory staging");
         memset(R.ctr_h, 0, sizeof(RefCounters));
     }
@@ -4566,20 +4242,7 @@ int kwok_refs_bind(kwok_engine* e, const int32_t* handles, const char* arena, co
     }
     if (al && !arena) return KWOK_EINVAL;
     int rc = 0;
-    if (n > R.bcap) {
-        dfree(R.b_off), dfree(R.b_len), dfree(R.q_h);
-        R.bcap = 0;
-        const size_t cap = std::max<size_t>(n + n / 4, 4096);
-        if ((rc = dalloc(e, &R.b_off, 2 * cap)) || (rc = dalloc(e, &R.b_len, 2 * cap)) || (rc = dalloc(e, &R.q_h, cap))) return rc;
-        R.bcap = cap;
-    }
-    if (al + 1 > R.acap) {
-        dfree(R.b_arena);
-        R.acap = 0;
-        const size_t cap = std::max<size_t>(al + al / 4 + 1, 1 << 16);
-        if ((rc = dalloc(e, &R.b_arena, cap))) return rc;
-        R.acap = cap;
-    }
+    if ((rc = R.spans.reserve(e, n)) || (rc = R.arena.reserve(e, al + 1, grown(al) + 1))) return rc;
     hipStream_t st = e->st;
     HIPCHK(e, hipMemcpyAsync(R.q_h, handles, n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(e, hipMemcpyAsync(R.b_off, ns_off, n * 8, hipMemcpyHostToDevice, st));
@@ -4607,14 +4270,7 @@ int kwok_refs_lookup(kwok_engine* e, int kind, const int32_t* handles, size_t n,
     drain(e);
     if (e->poisoned) return poisoned(e);
     if (!n) return KWOK_OK;
-    if (n > R.bcap) {  // (q_h is sized with the bind's buffers)
-        dfree(R.b_off), dfree(R.b_len), dfree(R.q_h);
-        R.bcap = 0;
-        const size_t cap = std::max<size_t>(n + n / 4, 4096);
-        int rc = 0;
-        if ((rc = dalloc(e, &R.b_off, 2 * cap)) || (rc = dalloc(e, &R.b_len, 2 * cap)) || (rc = dalloc(e, &R.q_h, cap))) return rc;
-        R.bcap = cap;
-    }
+    if (int rc = R.spans.reserve(e, n)) return rc;  // (q_h is sized with the bind's buffers)
     HIPCHK(e, hipMemcpyAsync(R.q_h, handles, n * 4, hipMemcpyHostToDevice, e->st));
     return refs_query(e, "kwok_refs_lookup", R.q_h, 0, n, kind == KWOK_KIND_PODS, (flags & KWOK_REFS_ANY_SLOT) != 0, refs, blob,
                       blob_cap, blob_used);
@@ -4659,8 +4315,8 @@ int kwok_refs_stats(kwok_engine* e, uint64_t out[KWOK_REFS_STAT_COUNT]) {
     out[KWOK_REFS_STAT_READS] = R.ctr_h->reads;
     out[KWOK_REFS_STAT_NOT_FOUND] = R.ctr_h->not_found;
     out[KWOK_REFS_STAT_BYTES] = (uint64_t)e->PLa * (KWOK_REF_STRIDE + sizeof(uint16_t)) + sizeof(RefCounters) +
-                                (uint64_t)R.qcap * (8 + 8 + 4 + sizeof(kwok_ref)) + R.tmp_bytes + R.blob_cap +
-                                (uint64_t)R.bcap * (2 * 8 + 2 * 4 + 4) + R.acap;
+                                (uint64_t)R.items.cap * (8 + 8 + 4 + sizeof(kwok_ref)) + R.tmp_bytes + R.blob.cap +
+                                (uint64_t)R.spans.cap * (2 * 8 + 2 * 4 + 4) + R.arena.cap;
     return KWOK_OK;
 }
 
@@ -4752,7 +4408,7 @@ int kwok_cni_assign(kwok_engine* e, const int32_t* handles, const uint32_t* ips,
     HIPCHK(e, hipMemcpyAsync(G.keys, handles, n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(e, hipMemcpyAsync(G.keys_sorted, ips, n * 4, hipMemcpyHostToDevice, st));
     HIPCHK(e, hipMemcpyAsync(G.idx_sorted, wr.data(), n, hipMemcpyHostToDevice, st));
-    launch_cni_assign(e->S, (const int32_t*)G.keys, G.keys_sorted, (const uint8_t*)G.idx_sorted, (uint32_t)n,
+    launch_cni_assign(e->S, (const int32_t*)G.keys.p, G.keys_sorted, (const uint8_t*)G.idx_sorted.p, (uint32_t)n,
                       G.out_status, &G.sum->rejected, st);
     HIPCHK(e, hipGetLastError());
     if ((rc = read_summary(e))) return rc;
