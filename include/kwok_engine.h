@@ -499,6 +499,7 @@ enum { KWOK_STAT_TICKS_FULL = 0 /* ticks that wrote every body: the full tick ke
        KWOK_STAT_ONCE_SUMMARY /* counting-kernel launches (either kind) that read the per-bucket summaries, not the pod rows */,
        KWOK_STAT_TICKS_HB_DELTA /* ticks whose heartbeat stream rewrote only the lines that changed (KWOK_HB_DELTA) */,
        KWOK_STAT_TICKS_ONCE_STREAM /* quiet ticks completed by the counting kernel beside the streamers (KWOK_ONCE_STREAM) */,
+       KWOK_STAT_TICKS_COUNT_REUSED /* quiet ticks that launched the streamers alone and took their count from the last clean one (KWOK_COUNT_REUSE); counted under the k_once_stream stats too */,
        KWOK_STAT_COUNT };
 int kwok_engine_stats(const kwok_engine* e, uint64_t out[KWOK_STAT_COUNT]);
 

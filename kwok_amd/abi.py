@@ -112,6 +112,10 @@ class WatchFrame(C.Structure):
                 ("uid", KwokStr), ("resource_version", KwokStr), ("name", KwokStr), ("namespace_", KwokStr)]
 
 
+ENGINE_STATS = ("ticks_full", "ticks_once", "once_redo", "once_summary", "ticks_hb_delta", "ticks_once_stream",
+                "ticks_count_reused")  # KWOK_STAT_* order
+
+
 LIST_ESC_KIND, LIST_ESC_RV, LIST_ESC_CONTINUE = 1, 2, 4
 LIST_STATS = ("bodies", "items", "host_items", "host_bodies", "body_bytes")  # KWOK_LIST_STAT_* order
 

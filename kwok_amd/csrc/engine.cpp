@@ -522,6 +522,19 @@ struct kwok_engine {
         uint64_t hb_prev = 0;       // this tick's stream is a delta against the bodies of this clock (0: all bytes)
         uint32_t hb_n = 0;          // bodies this tick's stream lays out
         bool hb_record = false;     // retire may record this tick's bodies (not requeued, no layout fault, streamed)
+        // What `hb_nodes` provably holds: the n handles of a count of state generation gen.
+        // Follows HbValid: written by retire of a clean k_once_stream tick in this slot
+        // (counted, or reused: the list it found), cleared by every enqueue into the slot
+        // and by alloc_slot (the lists are allocated once).  A reused tick needs an exact match.
+        struct ListValid {
+            bool ok = false;
+            const int32_t* list = nullptr;
+            uint32_t n = 0;
+            uint64_t gen = 0;
+        } list_valid;
+        bool count_reused = false;  // launched as k_hb_stream: the count is the engine's clean-count record
+        bool requeued = false;      // the launch in flight is a requeue (the first one skipped, or the tick was redone)
+        uint64_t state_gen = 0;     // the engine's state generation at the tick's enqueue
         // the tick in the slot
         int state = 0;  // SLOT_FREE, SLOT_QUEUED (enqueued), SLOT_DONE (finished on the host, not collected)
         uint64_t now = 0, target = 0;
@@ -599,6 +612,30 @@ struct kwok_engine {
     bool once_sum_ok = true;    // KWOK_ONCE_SUM=0: every k_once tick reads the pod rows (A/B)
     bool sum_valid = false;
     uint32_t sum_gen = 0;
+    // Count reuse.  k_once_stream's count (handle list, totals) reads
+    // node and pod state words, pod_fill, hb_bpre and the managed count, never `now`: a
+    // quiet tick that follows a cleanly counted one with none of those changed in between
+    // would count the same again, so it launches the streamers alone (k_hb_stream) and
+    // retire fills its header from the record.  state_gen is bumped wherever sum_valid is
+    // cleared (every ingest, CNI assignment, pool Put, zombie sweep, redo and k_tick launch)
+    // and by every node / pod batch, pod capacity growth and template upload besides;
+    // resync sweeps change state through the ingest paths.  A tick records the generation
+    // it was enqueued under; a reused tick has no net that finds unexpected work, so the
+    // generation alone decides.
+    bool count_reuse_ok = true;  // KWOK_COUNT_REUSE=0: every quiet tick counts (A/B, tests)
+    uint64_t state_gen = 1;
+    void state_changed() {
+        sum_valid = false;
+        state_gen++;
+    }
+    // the last clean count: written by retire alone, for a k_once_stream tick that counted
+    // and completed without error, redo, device skip or requeue; tot is the device-written
+    // part of its header (before derive_header), gen the generation it was enqueued under
+    struct CleanCount {
+        bool ok = false;
+        uint64_t gen = 0;
+        uint64_t tot[16] = {};
+    } clean_count;
     uint64_t stats[KWOK_STAT_COUNT] = {};  // kwok_engine_stats
     uint8_t* dump_h = nullptr;  // kwok_dump_pods' page-locked staging
     size_t dump_cap = 0;
@@ -859,6 +896,7 @@ int alloc_slot(kwok_engine* e, int k) {
     kwok_engine::TickSlot& T = e->slots[k];
     int rc = 0;
     T.hb_valid.ok = false;
+    T.list_valid.ok = false;
     if ((rc = dalloc(e, &T.hb_nodes, e->NLa)) || (rc = dalloc(e, &T.init_nodes, e->NLa)) ||
         (rc = dalloc(e, &T.init_off, e->NLa)) || (rc = dalloc(e, &T.init_len, e->NLa)) ||
         (rc = dalloc(e, &T.pp_pods, e->PLa)) || (rc = dalloc(e, &T.pp_off, e->PLa)) || (rc = dalloc(e, &T.pp_len, e->PLa)) ||
@@ -1014,6 +1052,7 @@ int exchange(kwok_engine* e, void* send, size_t bytes, void* recv) {
 int grow_pods(kwok_engine* e, uint32_t new_cp) {
     const uint32_t old = e->Cp, nb = e->nb;
     if (new_cp <= old) return KWOK_OK;
+    e->state_changed();  // (the pod rows move)
     hipStream_t st = e->st;
     DevState& S = e->S;
     const size_t PL2 = (size_t)nb * new_cp, PLa2 = PL2 + 16;
@@ -1511,6 +1550,8 @@ int kwok_engine_create(const kwok_config* cfg, kwok_engine** out) {
         e->once_ok = !(on && on[0] == '0');
         const char* ost = getenv("KWOK_ONCE_STREAM");
         e->once_stream_ok = !(ost && ost[0] == '0');
+        const char* cre = getenv("KWOK_COUNT_REUSE");
+        e->count_reuse_ok = !(cre && cre[0] == '0');
         const char* os = getenv("KWOK_ONCE_SUM");
         e->once_sum_ok = !(os && os[0] == '0');
         const char* zc = getenv("KWOK_INGEST_ZC");
@@ -1597,6 +1638,7 @@ int kwok_engine_create(const kwok_config* cfg, kwok_engine** out) {
         if (r == hipSuccess) r = hipStreamSynchronize(e->st);
         if (r != hipSuccess) return bail(e->fail(KWOK_EDEVICE, "template upload: %s", hipGetErrorString(r)));
         e->hb_gen++;  // (the template and `start` are fixed from here on: nothing else bumps it)
+        e->state_changed();
         for (auto& T : e->slots) T.hb_valid.ok = false;
     }
     {
@@ -1860,7 +1902,7 @@ int kwok_ingest_nodes(kwok_engine* e, const kwok_node_event* ev, size_t n, const
     if (e->poisoned) return poisoned(e);
     e->emit_hint = true;
     e->quiet = 0;
-    e->sum_valid = false;
+    e->state_changed();
     if (!n) return 0;
     int rc = node_reserve(e, n, arena_len);
     if (rc) return rc;
@@ -1870,6 +1912,7 @@ int ingest_nodes_impl(kwok_engine* e, const kwok_node_event* ev, size_t n, const
                       int32_t* out_handles, int32_t* out_status, const NodeJsonCtx* nj) {
     const auto t0 = clk::now();
     int rc = 0;
+    e->state_changed();  // (every node batch, whatever its entry point: node states, hb_bpre, the managed count)
     if (e->refs.on && n) e->refs.gen[KWOK_KIND_NODES]++;  // (kwok_read_refs' stale guard: the batch may create nodes)
     auto& G = e->ing;
     hipStream_t st = e->st;
@@ -2069,7 +2112,7 @@ int ingest_pods_impl(kwok_engine* e, const void* recs, int packed, size_t n, con
     }
     e->emit_hint = true;
     e->quiet = 0;
-    e->sum_valid = false;
+    e->state_changed();
     if (!n) return tick_now >= 0 ? tick_submit_impl(e, tick_now) : 0;
     if (e->refs.on) e->refs.gen[KWOK_KIND_PODS]++;  // (kwok_read_refs' stale guard: the batch may create pods)
     e->pod_records_since_tick += n;
@@ -2790,7 +2833,7 @@ int ingest_nodes_json_impl(kwok_engine* e, const kwok_codec* c, const char* aren
     if (e->poisoned) return poisoned(e);
     e->emit_hint = true;
     e->quiet = 0;
-    e->sum_valid = false;
+    e->state_changed();
     if (n_host) *n_host = 0;
     if (!n) return 0;
     const auto t0 = clk::now();
@@ -3435,7 +3478,7 @@ int kwok_resync_sweep(kwok_engine* e, int kind, int32_t* out_handles, size_t cap
     } else {
         e->emit_hint = true;
         e->quiet = 0;
-        e->sum_valid = false;
+        e->state_changed();
         const std::unordered_map<uint32_t, uint32_t> hdoc;
         const std::vector<kwok_node_event> hrec;
         const std::vector<std::string> hbuf;
@@ -4390,7 +4433,7 @@ int kwok_cni_assign(kwok_engine* e, const int32_t* handles, const uint32_t* ips,
     if (e->poisoned) return poisoned(e);
     if (!n) return 0;
     e->quiet = 0;
-    e->sum_valid = false;
+    e->state_changed();
     // a handle assigned twice keeps its last valid IP (configurePod runs once per tick)
     std::vector<uint8_t> wr(n, 0);
     {
@@ -4426,7 +4469,7 @@ int kwok_pool_put(kwok_engine* e, const uint32_t* ips, size_t n) {
     if (e->poisoned) return poisoned(e);
     e->puts.insert(e->puts.end(), ips, ips + n);
     e->quiet = 0;
-    e->sum_valid = false;
+    e->state_changed();
     e->foreign_ips = true;  // releases of another rank's pods (multi rank)
     return flush_ops(e);
 }
@@ -4475,6 +4518,8 @@ int enqueue_tick(kwok_engine* e, int k, bool requeue) {
         T.hb_record = !requeue && !fault_tick && !e->no_stream && !S.hb_once && !e->multi;
         T.hb_valid.ok = false;  // the region is being rewritten: known again when this tick retires
     }
+    T.requeued = requeue;
+    T.state_gen = e->state_gen;
     if (e->hb_pre_dirty) {
         // heartbeat handles are written in node order at per-chain-block bases:
         // managed nodes of the buckets before each block's range (k_hb_pre, from
@@ -4530,8 +4575,18 @@ int enqueue_tick(kwok_engine* e, int k, bool requeue) {
              S.cn <= (uint32_t)ONCE_NODE_LDS && e->PL < (1u << ONCE_FIELD_BITS) && e->NL < (1u << ONCE_FIELD_BITS) &&
              (S.hb_once || (e->once_stream_ok && e->n_stream > 0 && !e->no_stream && !e->pp_followup));
     T.once_stream = T.once && !S.hb_once;
+    // count reuse: the engine holds a clean count of this very state and the slot's handle list
+    // is that count's - the streamers alone (k_hb_stream); retire fills the header from the record
+    {
+        const kwok_engine::TickSlot::ListValid L = T.list_valid;
+        const kwok_engine::CleanCount& C = e->clean_count;
+        T.list_valid.ok = false;  // (whatever runs may write the list: known again when this tick retires)
+        T.count_reused = T.once_stream && !requeue && !fault_tick && e->count_reuse_ok && C.ok && C.gen == e->state_gen &&
+                         C.tot[AG_HB] == nhb && L.ok && L.list == T.hb_nodes && L.n == nhb && L.gen == e->state_gen;
+    }
     // (k_once_stream's counting blocks are done in ~10 us: the stream is the streamers')
     S.stream_share = e->n_stream == 0 ? 0u
+                     : T.count_reused  ? 1024u  // (nobody else to write a tail)
                      : e->share_env >= 0 ? (uint32_t)e->share_env
                                          : (hb_bytes < (32ull << 20) || T.split || T.hb_prev || T.once_stream ? 1024u
                                             : S.hb_nt                                        ? 860u
@@ -4567,7 +4622,10 @@ int enqueue_tick(kwok_engine* e, int k, bool requeue) {
         // region past the Infinity Cache (hb_nt's size).  1M x 10M: 0.1146 ms per step with one,
         // 0.1088 with two; 100k x 1M: 0.0156 with one, 0.0177 with two (profiles/q1_layout_ab.txt)
         const uint32_t n_os = e->n_once_stream ? e->n_once_stream : hb_bytes >= (256ull << 20) ? 2 * e->n_stream : e->n_stream;
-        if (T.once_stream)
+        if (T.count_reused)
+            launch_hb_stream(S, n_os, now, (uint64_t)e->start, nhb, prof & (TICK_PROF | TICK_NOSTREAM), T.hb_prev, st,
+                             ev ? ev[0] : nullptr, ev ? ev[1] : nullptr);
+        else if (T.once_stream)
             launch_tick_once_stream(S, n_os, now, (uint64_t)e->start, nhb, prof & (TICK_PROF | TICK_NOSTREAM), mode,
                                     e->sum_gen, T.hb_prev, st, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr);
         else
@@ -4576,13 +4634,13 @@ int enqueue_tick(kwok_engine* e, int k, bool requeue) {
         HIPCHK(e, hipGetLastError());
         qstamp(2);
     } else if (!e->multi) {
-        e->sum_valid = false;  // (a k_tick may change pod states)
+        e->state_changed();  // (a k_tick may change pod states)
         launch_tick(S, e->n_stream, now, (uint64_t)e->start, nhb, TICK_FRONT | TICK_BACK | prof, T.tag, T.target, st,
                     ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, T.hb_prev);
         HIPCHK(e, hipGetLastError());
         qstamp(2);
     } else {
-        e->sum_valid = false;
+        e->state_changed();
         launch_tick(S, e->n_stream, now, (uint64_t)e->start, nhb, TICK_FRONT | prof, T.tag, T.target, st,
                     ev ? ev[0] : nullptr, ev ? ev[1] : nullptr);
         // one allgather of the fixed-size exchange message, then BACK: it folds the
@@ -4761,10 +4819,14 @@ void jobs_trace_dump(kwok_engine* e) {
 
 // per stamp k: earliest / median / latest block, microseconds after the earliest block start
 void trace_tick(kwok_engine* e) {
-    const size_t G = e->S.n_chain, N = G + e->n_stream;
+    // (the rows allocated: k_once_stream and k_hb_stream run up to two streamer blocks per CU)
+    const size_t G = e->S.n_chain, N = G + std::max(2 * e->n_stream, e->n_once_stream);
     static const int skip = getenv("KWOK_TICK_TRACE_SKIP") ? atoi(getenv("KWOK_TICK_TRACE_SKIP")) : 5;
     static const uint64_t only = getenv("KWOK_TICK_TRACE_COUNT") ? strtoull(getenv("KWOK_TICK_TRACE_COUNT"), nullptr, 10) : 0;
-    if ((int)++e->trace_seen <= skip) return;  // skip the initial (bulk) ticks
+    if ((int)++e->trace_seen <= skip) {  // skip the initial (bulk) ticks; their stamps go (not every kernel writes every row)
+        (void)hipMemsetAsync(e->S.trace, 0, N * TRACE_SLOTS * 8, e->st);
+        return;
+    }
     if (only && e->trace_ticks >= only) return;  // KWOK_TICK_TRACE_COUNT: summarise only the first traced ticks
     const size_t TS = TRACE_SLOTS;
     e->trace_h.assign(N * TS, 0);
@@ -4773,6 +4835,11 @@ void trace_tick(kwok_engine* e) {
         return;
     uint64_t t0 = ~0ull;
     for (size_t b = 0; b < G; b++) t0 = std::min(t0, e->trace_h[b * TS]);
+    if (t0 == 0) {  // no chain or counting block ran (k_hb_stream): after the first streamer's start
+        t0 = ~0ull;
+        for (size_t b = G; b < N; b++)
+            if (e->trace_h[b * TS]) t0 = std::min(t0, e->trace_h[b * TS]);
+    }
     // stamps a block did not reach this tick (a clean block skips the pool phase) are 0
     auto summarise = [&](size_t lo, size_t hi, int k, double* out) {
         std::vector<double> v;
@@ -4833,7 +4900,7 @@ void trace_tick(kwok_engine* e) {
 int redo_tick(kwok_engine* e, int k) {
     kwok_engine::TickSlot& T = e->slots[k];
     e->stats[KWOK_STAT_ONCE_REDO]++;
-    e->sum_valid = false;
+    e->state_changed();
     memset(T.hdr_h, 0, sizeof(TickHdr));
     HIPCHK(e, hipMemsetAsync(&e->S.bar->skip, 0, sizeof(uint32_t), e->st));
     T.no_once = true;
@@ -4891,6 +4958,9 @@ int retire(kwok_engine* e) {
     }
     if (e->multi && T.hdr_h->xforeign) e->global_foreign = true;  // (the BACK launch that ran to the end)
     bool requeue_next = false;
+    // a reused count: the totals the clean count published (k_hb_stream writes no header;
+    // a launch that skipped on the device was enqueued again as a counting tick)
+    if (T.count_reused) memcpy(T.hdr_h->tot, e->clean_count.tot, sizeof(T.hdr_h->tot));
     if (T.once && T.hdr_h->redo) {
         if (int rc = redo_tick(e, k)) return failed(rc);
         requeue_next = next >= 0 && e->slots[next].state == SLOT_QUEUED;
@@ -4949,8 +5019,14 @@ int retire(kwok_engine* e) {
         (void)release_for_host(e);
         (void)hipMemcpyAsync(&send, &e->S.bar->stream_end_max, 8, hipMemcpyDeviceToHost, e->st);
         (void)hipMemsetAsync(&e->S.bar->stream_end_max, 0, 8, e->st);
+        unsigned long long nent = 0;  // (k_hb_stream: no counting block publishes the earliest entry)
+        if (T.count_reused) {
+            (void)hipMemcpyAsync(&nent, &e->S.bar->neg_entry_max, 8, hipMemcpyDeviceToHost, e->st);
+            (void)hipMemsetAsync(&e->S.bar->neg_entry_max, 0, 8, e->st);
+        }
         (void)hipStreamSynchronize(e->st);
         T.hdr_h->clk[CLK_STREAM_END] = send;
+        if (T.count_reused) T.hdr_h->clk[CLK_ENTRY_MIN] = ~nent;
         auto span = [&](int a, int b) { return H.clk[b] > H.clk[a] ? (double)(H.clk[b] - H.clk[a]) * 1e-5 : 0.0; };
         const double classify = span(CLK_ENTRY_MIN, CLK_P1_MAX), stream = span(CLK_ENTRY_MIN, CLK_STREAM_END);
         const double header = span(CLK_P1_MAX, CLK_HDR), pool = span(CLK_BACK, CLK_POOL);
@@ -4970,7 +5046,7 @@ int retire(kwok_engine* e) {
     // entries go (k_free_zombies, queued on the engine stream: a tick already
     // queued behind this one reads no such node; every ingest follows it)
     if (H.n_del) {
-        e->sum_valid = false;
+        e->state_changed();
         launch_free_zombies(e->S, e->st);
         if (hipGetLastError() != hipSuccess) return failed(e->fail(KWOK_EDEVICE, "k_free_zombies"));
     }
@@ -4997,6 +5073,20 @@ int retire(kwok_engine* e) {
     e->host_ticks++;
     e->stats[T.once && !T.once_stream ? KWOK_STAT_TICKS_ONCE : KWOK_STAT_TICKS_FULL]++;
     if (T.once_stream) e->stats[KWOK_STAT_TICKS_ONCE_STREAM]++;
+    if (T.count_reused) e->stats[KWOK_STAT_TICKS_COUNT_REUSED]++;
+    // a k_once_stream tick that completed cleanly (no error or overflow: returned above; not
+    // redone, not requeued after a device skip): its count is the engine's clean count, and the
+    // slot's handle list is that count's, as is a reused tick's (nothing wrote it)
+    if (T.once_stream && !T.requeued && !T.no_once) {
+        if (!T.count_reused) {
+            e->clean_count.ok = true;
+            e->clean_count.gen = T.state_gen;
+            memcpy(e->clean_count.tot, H.tot, sizeof(H.tot));
+        }
+        kwok_engine::TickSlot::ListValid& L = T.list_valid;
+        L.list = T.hb_nodes, L.n = H.n_hb, L.gen = T.state_gen;
+        L.ok = true;
+    }
     e->pp_followup = !e->S.cni && H.n_pp != H.n_alloc_local;
     // the slot's heartbeat region now holds this tick's bodies (TickSlot::HbValid); a
     // tick that was redone records nothing (hb_record: no heartbeat-once engine, no requeue)

@@ -184,6 +184,10 @@ uint32_t once_blocks(const DevState& S);
 void launch_tick_once_stream(const DevState& S, uint32_t n_stream, uint64_t now, uint64_t start, uint32_t n_hb, int phases,
                              uint32_t sum_mode, uint32_t gen, uint64_t hb_prev, hipStream_t st, hipEvent_t t0 = nullptr,
                              hipEvent_t t1 = nullptr);
+// ... whose count the host holds from an earlier tick (count reuse): the n_stream streamer
+// blocks alone write the whole stream (DevState::stream_share must be 1024)
+void launch_hb_stream(const DevState& S, uint32_t n_stream, uint64_t now, uint64_t start, uint32_t n_hb, int phases,
+                      uint64_t hb_prev, hipStream_t st, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
 // split ticks: the pod jobs (deletes, patch job records, state transitions) of
 // every dirty 64-group run of every chain block, one wave each
 // k_pod_jobs; a fused launch (DevState::fuse_pods) also writes the node inits with init_blocks blocks

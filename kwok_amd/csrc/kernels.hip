@@ -2794,6 +2794,46 @@ __global__ __launch_bounds__(64 * ONCE_WAVES, 2) void k_once_stream(DevState S, 
     }
 }
 
+// ---------------------------------------------------------------------------
+// k_hb_stream: a quiet tick whose count the host already holds (engine.cpp,
+// count reuse: nothing has changed a state word, hb_bpre, the managed count or
+// the template since a k_once_stream tick counted cleanly, and the slot's handle
+// list is that count's).  k_once_stream's streamer branch alone, with the whole
+// stream (the host sets stream_share to 1024: nobody else writes a tail), and
+// the arrivals a completed count would have added to GridBar::arrive.
+// ---------------------------------------------------------------------------
+template <bool GEN_HB>
+__global__ __launch_bounds__(64 * ONCE_WAVES, 2) void k_hb_stream(DevState S, uint64_t now_unix, uint64_t start_unix,
+                                                                 uint32_t n_hb, int phases, uint64_t prev_unix) {
+    constexpr int NT = 64 * ONCE_WAVES;
+    __shared__ uint4 hb_tmpl4[HB_MAX_UNITS];
+    __shared__ HbDelta hb_delta;
+    uint8_t* hb_tmpl = reinterpret_cast<uint8_t*>(hb_tmpl4);
+    const uint32_t t = threadIdx.x, b = blockIdx.x;
+    if (ld32_sc1(&S.bar->skip)) return;  // queued behind a tick the host must finish (re-enqueued then, with a count)
+    if (S.trace && t == 0) S.trace[(size_t)(S.n_chain + b) * TRACE_SLOTS] = __builtin_amdgcn_s_memrealtime();
+    if ((phases & TICK_PROF) && t == 0 && b < 8u)
+        atomicMax(&S.bar->neg_entry_max, ~(unsigned long long)__builtin_amdgcn_s_memrealtime());
+    if (b == 0 && t == 0)  // (GridBar::arrive is cumulative: once_publish's add of a completed count)
+        __hip_atomic_fetch_add(&S.bar->arrive, (unsigned long long)S.n_chain, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    build_hb_template<NT>(S, hb_tmpl, now_unix, start_unix);
+    if (!(phases & TICK_NOSTREAM))
+        hb_write_share<GEN_HB, NT>(S, hb_tmpl4, &hb_delta, prev_unix, hb_bodies(S, n_hb), true, b, gridDim.x);
+    if ((phases & TICK_PROF) && t == 0) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        atomicMax(&S.bar->stream_end_max, (unsigned long long)__builtin_amdgcn_s_memrealtime());
+    }
+    if (S.trace && t == 0) S.trace[(size_t)(S.n_chain + b) * TRACE_SLOTS + 6] = __builtin_amdgcn_s_memrealtime();
+}
+
+void launch_hb_stream(const DevState& S, uint32_t n_stream, uint64_t now, uint64_t start, uint32_t n_hb, int phases,
+                      uint64_t hb_prev, hipStream_t st, hipEvent_t t0, hipEvent_t t1) {
+    auto kern = S.hb_units == (uint32_t)HB_CHUNKS ? k_hb_stream<false> : k_hb_stream<true>;
+    if (t0)
+        hipExtLaunchKernelGGL(kern, dim3(n_stream), dim3(64 * ONCE_WAVES), 0, st, t0, t1, 0, S, now, start, n_hb, phases, hb_prev);
+    else hipLaunchKernelGGL(kern, dim3(n_stream), dim3(64 * ONCE_WAVES), 0, st, S, now, start, n_hb, phases, hb_prev);
+}
+
 uint32_t once_blocks(const DevState& S) { return (S.nb + ONCE_WAVES - 1) / ONCE_WAVES; }
 
 void launch_tick_once(const DevState& S, uint64_t now, uint64_t start, uint32_t n_hb, int phases, uint32_t sum_mode,

@@ -929,13 +929,13 @@ class Engine(EngineBase):
     def read_wait(self):
         self._check(self._lib.kwok_read_wait(self._h), "read_wait")
 
-    STATS = ("ticks_full", "ticks_once", "once_redo", "once_summary", "ticks_hb_delta",
-             "ticks_once_stream")  # KWOK_STAT_* order
+    STATS = abi.ENGINE_STATS  # KWOK_STAT_* order
 
     def stats(self):
         """kwok_engine_stats: ticks run by k_tick / completed by k_once / k_once ticks redone / k_once
         launches that read the per-bucket summaries / k_tick ticks whose heartbeat stream rewrote only
-        the lines that changed since the slot's previous tick"""
+        the lines that changed since the slot's previous tick / quiet ticks completed by the counting
+        kernel beside the streamers / those of them that reused the last clean count (streamers only)"""
         out = (C.c_uint64 * len(self.STATS))()
         self._check(self._lib.kwok_engine_stats(self._h, out), "engine_stats")
         return dict(zip(self.STATS, list(out)))

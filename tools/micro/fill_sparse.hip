@@ -13,6 +13,10 @@
 //   set 1  two changed bytes per Now value (minute carry: minutes and tens of seconds)
 // The passes alternate between two regions, as the engine's two tick slots do.
 // The full fill (fill_hbm's grp-nt) runs first as the yardstick, with its spread.
+// Last, the l64 pass once more with every cache-policy form of the 16-byte vector
+// store (global_store_dwordx4 with nt / sc0 / sc1 in each combination; sc0 sc1 is
+// the write-through, system-scope form), plain and nt among them as the run's own
+// reference.
 // usage: fill_sparse [n_hb] [--pmc]   (--pmc: 3 passes per variant and no timing,
 // for rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE; the variant is in the kernel name)
 // build: hipcc --offload-arch=gfx950 -O3 -I kwok_amd/csrc tools/micro/fill_sparse.hip
@@ -79,7 +83,47 @@ __global__ __launch_bounds__(256) void k_sparse(u32x4* dst, uint64_t n_hb, uint3
     }
 }
 
+// k_sparse's l64 walk with the store's cache policy spelled out: POL bit 0 nt, bit 1 sc0, bit 2 sc1
+template <int POL>
+__device__ __forceinline__ void store_pol(u32x4* p, u32x4 v) {
+    if (POL == 0) asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(p), "v"(v) : "memory");
+    if (POL == 1) asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(p), "v"(v) : "memory");
+    if (POL == 2) asm volatile("global_store_dwordx4 %0, %1, off sc0" ::"v"(p), "v"(v) : "memory");
+    if (POL == 3) asm volatile("global_store_dwordx4 %0, %1, off sc0 nt" ::"v"(p), "v"(v) : "memory");
+    if (POL == 4) asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
+    if (POL == 5) asm volatile("global_store_dwordx4 %0, %1, off sc1 nt" ::"v"(p), "v"(v) : "memory");
+    if (POL == 6) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
+    if (POL == 7) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" ::"v"(p), "v"(v) : "memory");
+}
+template <int POL, int SET, int BPC>
+__global__ __launch_bounds__(256) void k_sparse_pol(u32x4* dst, uint64_t n_hb, uint32_t GS, const uint16_t* el_g, uint32_t n_e) {
+    __shared__ uint16_t el[MAX_E];
+    __shared__ u32x4 tmpl[U];
+    for (uint32_t i = threadIdx.x; i < n_e; i += blockDim.x) el[i] = el_g[i];
+    for (uint32_t i = threadIdx.x; i < U; i += blockDim.x) tmpl[i] = u32x4{i, 1u, 2u, 3u};
+    __syncthreads();
+    if (!n_e) return;
+    const uint64_t units = n_hb * U, GU = (uint64_t)GS * U;
+    const uint64_t ng = (n_hb + GS - 1) / GS, g0 = ng * blockIdx.x / gridDim.x, g1 = ng * (blockIdx.x + 1) / gridDim.x;
+    const uint32_t step = blockDim.x, dg = step / n_e, dr = step % n_e;
+    uint64_t g = g0 + threadIdx.x / n_e;
+    uint32_t r = threadIdx.x % n_e;
+    while (g < g1) {
+        const uint32_t u = el[r];
+        const uint64_t i = g * GU + u;
+        if (i < units) store_pol<POL>(dst + i, tmpl[u % U]);
+        g += dg;
+        r += dr;
+        if (r >= n_e) r -= n_e, g++;
+    }
+}
+
 typedef void (*sparse_fn)(u32x4*, uint64_t, uint32_t, const uint16_t*, uint32_t);
+template <int POL>
+static sparse_fn pick_pol(int set, int bpc) {
+    return set == 0 ? (bpc == 1 ? k_sparse_pol<POL, 0, 1> : k_sparse_pol<POL, 0, 2>)
+                    : (bpc == 1 ? k_sparse_pol<POL, 1, 1> : k_sparse_pol<POL, 1, 2>);
+}
 template <int NT, int P, int SET>
 static sparse_fn pick_bpc(int bpc) {
     return bpc == 1 ? k_sparse<NT, P, SET, 1> : k_sparse<NT, P, SET, 2>;
@@ -178,5 +222,30 @@ int main(int argc, char** argv) {
                     });
                 }
         }
+    // the l64 pass under every cache-policy form of the vector store
+    static const char* pol_name[8] = {"plain", "nt", "sc0", "sc0 nt", "sc1", "sc1 nt", "sc0 sc1", "sc0 sc1 nt"};
+    for (int set = 0; set < 2; set++) {
+        const uint32_t GS = 4, GU = GS * U;
+        std::vector<uint16_t> el;
+        for (uint32_t p0 = 0; p0 < GU; p0 += 4) {
+            bool d = false;
+            for (uint32_t u = p0; u < p0 + 4; u++) d |= dirty[set][u % U];
+            if (d)
+                for (uint32_t u = p0; u < p0 + 4; u++) el.push_back((uint16_t)u);
+        }
+        if (hipMemcpy(el_d, el.data(), el.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return 1;
+        const double bytes = (double)((n_hb + GS - 1) / GS) * el.size() * 16;
+        for (int pol = 0; pol < 8; pol++)
+            for (int bpc : {1, 2}) {
+                char name[64];
+                snprintf(name, sizeof name, "set %d l64 [%s] b/CU %d", set, pol_name[pol], bpc);
+                sparse_fn fn = pol == 0 ? pick_pol<0>(set, bpc) : pol == 1 ? pick_pol<1>(set, bpc) : pol == 2 ? pick_pol<2>(set, bpc)
+                             : pol == 3 ? pick_pol<3>(set, bpc) : pol == 4 ? pick_pol<4>(set, bpc) : pol == 5 ? pick_pol<5>(set, bpc)
+                             : pol == 6 ? pick_pol<6>(set, bpc) : pick_pol<7>(set, bpc);
+                measure(name, bytes, [&](u32x4* d) {
+                    hipLaunchKernelGGL(fn, dim3(cus * bpc), dim3(256), 0, 0, d, n_hb, GS, el_d, (uint32_t)el.size());
+                });
+            }
+    }
     return hipDeviceSynchronize() == hipSuccess ? 0 : 1;
 }
