@@ -1,4 +1,4 @@
-// device.h - layouts shared by the host runtime (engine.cpp) and the gfx950
+// device.h - layouts shared by the host runtime (engine.cpp, engine_tick.cpp) and the gfx950
 // kernels (kernels.hip).  Everything the kernels touch lives in HBM as
 // struct-of-arrays indexed by LOCAL slot (slot - first owned slot).
 #pragma once
@@ -183,7 +183,7 @@ constexpr int XINLINE = 2048;
 struct XMsg {
     uint64_t alloc, n_use, n_rel;
     uint64_t seq;  // the FRONT launch's tick tag: equal on every rank that ticks in step
-    uint64_t foreign;  // the rank's sticky foreign-IP flag (engine.cpp quiet ticks: Use checks skipped
+    uint64_t foreign;  // the rank's sticky foreign-IP flag (engine_tick.cpp quiet ticks: Use checks skipped
                        // only while no rank ever had one)
     uint64_t counters[16];
     uint32_t ips[XINLINE];  // uses then releases (when they fit)
@@ -258,7 +258,7 @@ struct IngSummary {
                             // creates > cp), else 0
     uint32_t foreign;       // an in-CIDR podIP the engine did not assign to that pod entered (or left) the
                             // pool: a create with a podIP, an update to another podIP, a Deleted event
-                            // releasing an address its pod does not hold (quiet ticks, engine.cpp)
+                            // releasing an address its pod does not hold (quiet ticks, engine_tick.cpp)
     uint32_t n_new;         // kwok_pod_rec12: the batch's KWOK_REC_NEW records up to this chunk
     uint32_t pad;
 };

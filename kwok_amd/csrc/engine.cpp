@@ -9,39 +9,12 @@
 //   NewController / NewNodeController / NewPodController  controller.go:80-152,
 //                                                          node_controller.go:79-117, pod_controller.go:84-128
 //   WatchNodes/ListNodes, WatchPods/ListPods event switch node_controller.go:256-295, pod_controller.go:301-367
-//   KeepNodeHeartbeat, LockNodes, LockPods, DeletePods    node_controller.go:175-204,301-354, pod_controller.go:155-250
 //   ipPool                                                utils.go:52-117
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <time.h>
-#include <string.h>
-#include <sys/mman.h>
+//
+// The tick queue (output slots and arena, enqueue / retire, submit / collect) is engine_tick.cpp;
+// engine_state.h holds the state both files work on.
+#include "engine_state.h"
 
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <functional>
-#include <map>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <unordered_map>
-#include <vector>
-
-#include "../../include/kwok_engine.h"
-#include "codec.h"
-#include "device.h"
-#include "gotemplate.h"
-#include "kernels.h"
-#include "echo.h"
-#include "templates.h"
-#include "engine_impl.h"
-
-using namespace kwok;
 
 namespace {
 
@@ -78,8 +51,6 @@ uint64_t json_spec_key(const std::vector<Container>& cs, const std::vector<Conta
 }
 
 thread_local std::string g_create_err;  // kwok_last_error(NULL) after a failed create
-using clk = std::chrono::steady_clock;
-double ms_between(clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
 
 uint32_t fnv1a32(const char* s, size_t n) {
     uint32_t h = 0x811C9DC5u;
@@ -90,617 +61,7 @@ uint32_t fnv1a32(const char* s, size_t n) {
     return h;
 }
 
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-};
-
-// Persistent host worker threads for the ingest partitions (started on first
-// use): run(n, f) calls f(0) on the caller and f(1..n-1) on the workers, and
-// returns when all are done.
-class WorkPool {
-  public:
-    ~WorkPool() {
-        {
-            std::lock_guard<std::mutex> l(m_);
-            stop_ = true;
-        }
-        cv_.notify_all();
-        for (auto& t : th_) t.join();
-    }
-    void run(int n, const std::function<void(int)>& f) {
-        while ((int)th_.size() < n - 1) {
-            const int id = (int)th_.size() + 1;
-            th_.emplace_back([this, id] { loop(id); });
-        }
-        {
-            std::lock_guard<std::mutex> l(m_);
-            job_ = &f;
-            width_ = n;
-            left_ = n - 1;
-            gen_++;
-        }
-        cv_.notify_all();
-        f(0);
-        std::unique_lock<std::mutex> l(m_);
-        done_.wait(l, [&] { return left_ == 0; });
-        job_ = nullptr;
-    }
-
-  private:
-    void loop(int id) {
-        uint64_t seen = 0;
-        std::unique_lock<std::mutex> l(m_);
-        for (;;) {
-            cv_.wait(l, [&] { return stop_ || gen_ != seen; });
-            if (stop_) return;
-            seen = gen_;
-            if (id >= width_) continue;  // this run uses fewer workers
-            const std::function<void(int)>* f = job_;
-            l.unlock();
-            (*f)(id);
-            l.lock();
-            if (--left_ == 0) done_.notify_one();
-        }
-    }
-    std::vector<std::thread> th_;
-    std::mutex m_;
-    std::condition_variable cv_, done_;
-    const std::function<void(int)>* job_ = nullptr;
-    uint64_t gen_ = 0;
-    int width_ = 0, left_ = 0;
-    bool stop_ = false;
-};
-
 }  // namespace
-
-struct kwok_engine {
-    kwok_config cfg{};
-    std::string err;
-    int W = 1, rank = 0, dev = 0;
-    int XW = 1;  // exchange messages per tick: W, or KWOK_EMULATE_RANKS on a one-rank multi engine (diagnostics)
-    bool multi = false;  // the FRONT / exchange / BACK tick (W > 1, or KWOK_FORCE_MULTI with one rank)
-    uint32_t B = 0, Cn = 0, Cp = 0, b_lo = 0, b_hi = 0, nb = 0, NL = 0, PL = 0;
-    uint32_t Hs = 0;  // pod handle stride: handle = bucket * Hs + slot in the bucket; Cp grows up to it
-    PoolGeom pool{};
-    uint32_t node_ip = 0;
-    std::string node_ip_s;
-    int64_t start = 0;
-    hipStream_t st = nullptr;   // tick pipeline
-    hipEvent_t fence = nullptr; // recorded (system-scope release) before device -> host copies of kernel output
-    hipStream_t rst = nullptr;  // kwok_read_outputs: copies of a collected tick, beside the next tick's kernels
-    // large arena reads split over more copy streams (KWOK_READ_STREAMS, default 1: two or
-    // four streams measured no faster than one, ~44 GB/s device-to-host either way)
-    int read_streams = 1;
-    hipStream_t rsx[3] = {};
-    hipEvent_t rd_go = nullptr, rd_part[3] = {};
-    DevState S{};
-
-    // ---- nodes: the directory (names -> slots), occupancy, managed / zombie counts
-    // live on the device (ingest.hip); the host keeps the managed-set size ----
-    uint64_t n_managed = 0;
-    bool hb_pre_dirty = true;                        // the per-chain-block heartbeat bases need k_hb_pre
-    uint32_t hb_epoch = 0;                           // kwok_tick_result.heartbeat_epoch: bumped when the managed set changes
-    uint32_t* d_hb_pre = nullptr;
-    uint32_t* d_hb_bpre = nullptr;                   // [nb + 1] per-bucket bases (k_once)
-    // pods: no host mirror.  The device's pod_state (USED = slot occupancy),
-    // pod_node and node_state (NS_SLOT) are the state the GPU ingest pass
-    // (ingest.hip) applies batches to; pod_fill is its per-bucket fill mark.
-    uint16_t* d_pod_fill = nullptr;
-
-    // ---- host work of node batches: the status strings of UPSERT records with a
-    // non-empty status (string checks, blob interning, custom node templates), on up
-    // to n_part host threads ----
-    int n_part = 1;
-    std::vector<uint32_t> puts;  // kwok_pool_put (other ranks' ingest-time releases), staged for flush_ops
-    void* pinned = nullptr;
-    size_t pinned_cap = 0;
-    void* d_ops = nullptr;
-    size_t d_ops_cap = 0;
-
-    // ---- GPU pod ingest (ingest.hip) ----
-    struct KWOK_LOCAL Ingest {
-        size_t sort_bytes = 0;
-        DevArr<void> d_ev;       // [recs.cap] kwok_pod_event, or the packed forms
-        DevArr<uint8_t> d_arena;
-        DevArr<PodRec> rec;
-        DevArr<uint32_t> keys, keys_sorted, idx_sorted;
-        DevArr<int32_t> out_handle, out_status;
-        DevArr<int8_t> out_status8;  // kwok_ingest_pods_packed: the statuses as bytes
-        DevArr<uint32_t> out_released;
-        DevArr<void> sort_tmp;   // [sort_bytes]
-        // kwok_ingest_pods_packed12: NEW records per 256-record tile, the tiles' prefixes,
-        // the creates' handles in create order
-        DevArr<uint32_t> tile_new, tile_pre;
-        DevArr<int32_t> new_handle;
-        static size_t ev_bytes(size_t cap) { return cap * sizeof(kwok_pod_event); }
-        static size_t sort_need(size_t cap) { return ingest_sort_bytes((uint32_t)cap, 32); }
-        // the per-record buffers (recs.cap: the records they hold) and the batch's strings
-        DevGroup recs{4096, {{d_ev, ev_bytes}, rec, keys, keys_sorted, idx_sorted, out_handle, out_status, out_released,
-                             out_status8, {tile_new, per_tile256}, {tile_pre, per_tile256}, new_handle, {sort_tmp, sort_need}}};
-        DevGroup arena{1 << 16, {d_arena}};
-        // per bucket (allocated once)
-        uint32_t *beg = nullptr, *end = nullptr;
-        uint32_t* abort = nullptr;          // [1] a chunk of the batch needs growth (speculative apply passes)
-        IngSummary* sums = nullptr;         // [nsums] one per chunk of a batch
-        IngSummary* sums_h = nullptr;       // pinned
-        size_t nsums = 0;
-        IngSummary* sum = nullptr;
-        // node batches (kwok_ingest_nodes): records, names, prepared records, host list
-        DevArr<kwok_node_event> d_nev;
-        DevArr<uint8_t> d_nnames;  // [nodes.cap * NAME_STRIDE]
-        DevArr<NodeRec> nrec;
-        DevArr<uint32_t> host_idx;
-        DevArr<NodeFix> d_nfix;
-        static size_t name_bytes(size_t cap) { return cap * NAME_STRIDE; }
-        DevGroup nodes{4096, {d_nev, {d_nnames, name_bytes}, nrec, host_idx, d_nfix}};
-        NodeSummary* nsum = nullptr;
-        NodeSummary* nsum_h = nullptr;  // pinned
-        Pinned<int32_t> res_h;          // [2 * nodes.cap]: handles, statuses
-        IngSummary* sum_h = nullptr;  // pinned
-        // a batch runs in chunks (KWOK_INGEST_CHUNK records): chunk k+1's prep reads its
-        // records over the link on `pst` while chunk k is applied and its results copied
-        // back on the engine stream
-        IngSummary* sum1 = nullptr;
-        hipStream_t pst = nullptr, dst = nullptr;  // prep (H2D + k_ing_prep) / results (D2H)
-        hipEvent_t tev[8] = {};  // KWOK_INGEST_PROF: device-side phase stamps of a two-chunk batch
-        hipEvent_t go = nullptr, prepped[2] = {nullptr, nullptr}, used[2] = {nullptr, nullptr};
-        hipEvent_t idone = nullptr;  // a pod batch's last operation (the host spins on it: KWOK_SYNC)
-        hipEvent_t rdone = nullptr;  // the results stream's work of a batch (kwok_pod_rec12: before the summaries)
-        size_t chunk = 1048576;
-        // the framed ingests (kwok_watch.h): the records' strings are in the resident watch
-        // stream, not in d_arena (null: d_arena)
-        const uint8_t* arena_src = nullptr;
-    } ing;
-
-    // ---- the watch stream framer (json.hip k_frame_*): the resident stream, its
-    // frames on the device and on the host, the caller's bytes (listed lines and
-    // documents are completed from them) ----
-    struct KWOK_LOCAL Watch {
-        DevArr<uint8_t> stream;        // [bytes.cap] the stream, padded to whole 16-byte windows
-        DevGroup bytes{1 << 16, {stream}};
-        uint64_t len = 0;
-        const char* host = nullptr;    // the caller's buffer (valid until the next framing call)
-        DevArr<uint32_t> tile_cnt, tile_base;
-        DevGroup tiles{1024, {tile_cnt, tile_base}};
-        DevArr<uint32_t> ends;         // [lines.cap] newline offsets
-        DevArr<kwok_watch_frame> frames;  // [lines.cap]
-        DevArr<uint32_t> host_list;    // [lines.cap]
-        DevGroup lines{4096, {ends, frames, host_list}};
-        DevArr<uint32_t> counts;       // [2]: newlines, listed lines
-        Pinned<uint32_t> counts_h;     // [2]
-        std::vector<kwok_watch_frame> frames_h;
-        uint64_t id = 0, next_id = 1;  // id 0: no stream resident
-        uint64_t stats[KWOK_WATCH_STAT_COUNT] = {};
-        // the List body framer (json.hip k_list_*): eight arrays of per-tile words,
-        // the candidates' `{` offsets (their `}` go to ends), its counters
-        DevArr<uint32_t> ltile;        // [8][ltiles.cap]
-        static size_t eight(size_t cap) { return 8 * cap; }
-        DevGroup ltiles{1024, {{ltile, eight}}};
-        DevArr<uint32_t> starts;       // [cands.cap]
-        DevGroup cands{4096, {starts}};
-        DevArr<uint32_t> lc;           // [KWOK_LIST_COUNTERS]
-        Pinned<uint32_t> lc_h;         // [KWOK_LIST_COUNTERS]
-        uint64_t lstats[KWOK_LIST_STAT_COUNT] = {};
-    } watch;
-
-    // ---- relist with Replace (resync.hip, kwok_watch.h): a `seen` byte per slot of each
-    // kind (allocated at the kind's first begin), the sweep's tile counts and outputs ----
-    struct KWOK_LOCAL Resync {
-        DevArr<uint8_t> pod_seen;      // [PLa] re-laid out with the pod arrays (grow_pods)
-        DevArr<uint8_t> node_seen;     // [NLa]
-        bool open[2] = {false, false}; // KWOK_KIND_*: a session is open (the ingests mark)
-        DevArr<ResyncCounters> ctr;
-        Pinned<ResyncCounters> ctr_h;
-        DevArr<uint32_t> tile_cnt, tile_base;
-        DevGroup tiles{1024, {tile_cnt, tile_base}};
-        DevArr<uint32_t> total;        // [1]
-        Pinned<uint32_t> total_h;      // [1]
-        DevArr<int32_t> d_handles, d_nodes;  // [swept.cap] the swept handles / their nodes, emit order
-        DevGroup swept{4096, {d_handles, d_nodes}};
-        DevArr<int32_t> d_mark;        // [marks.cap] kwok_resync_mark's handles
-        DevGroup marks{4096, {d_mark}};
-        uint64_t stats[KWOK_RESYNC_STAT_COUNT] = {};
-    } resync;
-
-    // ---- the pod uid directory (uid.hip, kwok_watch.h): a uid per pod slot, the table
-    // of hints, the per-call buffers of a by-uid framed batch and of bind / lookup ----
-    struct KWOK_LOCAL Uid {
-        struct Bytes {
-            uint8_t b[KWOK_UID_MAX];
-        };
-        bool on = false;
-        DevArr<Bytes> pod_uid;           // [PLa] re-laid out with the pod arrays (grow_pods)
-        DevArr<uint8_t> pod_uid_len;     // [PLa]
-        DevArr<unsigned long long> tab;
-        size_t tab_cap = 0;              // entries (a power of two)
-        int forced_log2 = 0;             // KWOK_UID_TAB_LOG2 (tests)
-        uint64_t live = 0, inserted = 0; // entries at the last rebuild; an upper bound of the inserts since
-        DevArr<UidCounters> ctr;
-        Pinned<UidCounters> ctr_h;
-        DevArr<UidRun> run;
-        Pinned<UidRun> run_h;
-        // per record of a by-uid batch
-        DevArr<uint32_t> fidx, uoff, res_rel;
-        DevArr<uint8_t> ulen, cls;
-        DevArr<uint64_t> hash;
-        DevArr<int32_t> res_h, res_st;
-        DevGroup recs{4096, {fidx, uoff, res_rel, ulen, cls, hash, res_h, res_st}};
-        DevArr<uint32_t> claim;
-        DevGroup claims{0, {claim}};     // (sized by claim_size: no headroom)
-        // bind / lookup: handles or results, spans, the caller's arena
-        DevArr<int32_t> q_h;
-        DevArr<uint64_t> q_off;
-        DevArr<uint32_t> q_len;
-        DevGroup spans{4096, {q_h, q_off, q_len}};
-        DevArr<uint8_t> q_arena;
-        DevGroup arena{1 << 16, {q_arena}};
-        // the by-uid batch whose records the ingest is applying (null: an entry that carries no uid)
-        const UidNote* note = nullptr;
-        std::vector<hipEvent_t> note_ev;  // KWOK_INGEST_PROF: stamps around each k_uid_note of a by-uid batch, in pairs
-        uint64_t stats[KWOK_UID_STAT_COUNT] = {};
-        UidDir dir() const { return UidDir{reinterpret_cast<uint8_t*>(pod_uid.p), pod_uid_len, tab, (uint32_t)(tab_cap - 1), ctr}; }
-    } uid;
-
-    // ---- the echo ledger (echo.hip, kwok_watch.h): the pool of noted uids behind its table,
-    // the per-call buffers of a filtered batch ----
-    struct KWOK_LOCAL Echo {
-        bool on = false;
-        DevArr<uint32_t> tab;
-        size_t tab_cap = 0;           // entries (a power of two)
-        DevArr<EchoEntry> pool;
-        size_t pool_cap = 0;
-        int forced_log2 = 0;          // KWOK_ECHO_TAB_LOG2 (tests)
-        DevArr<EchoCounters> ctr;
-        Pinned<EchoCounters> ctr_h;   // the counters after the last call
-        DevArr<EchoCall> call;
-        Pinned<EchoCall> call_h;
-        uint64_t rebuilds = 0;
-        // per record of a call
-        DevArr<uint32_t> uoff, roff, own, cnt, fill, lbase, list, fidx, bsum, kidx, kpos, q_len, res_rel;
-        DevArr<uint8_t> ulen, rlen, kind, res;
-        DevArr<uint64_t> hash, q_off;
-        DevArr<int32_t> hdrop, res_h, res_st;
-        DevGroup recs{4096, {uoff, roff, own, cnt, fill, lbase, list, fidx, {bsum, per_tile256}, kidx, kpos, q_len, res_rel,
-                             ulen, rlen, kind, res, hash, q_off, hdrop, res_h, res_st}};
-        DevArr<uint32_t> claim;
-        DevGroup claims{0, {claim}};  // (sized by claim_size: no headroom)
-        // the typed front end: spans, ops, statuses and the caller's arena
-        DevArr<uint64_t> s_uoff, s_roff;
-        DevArr<uint32_t> s_ulen, s_rlen;
-        DevArr<uint8_t> s_op;
-        DevArr<int32_t> s_status;
-        DevGroup spans{4096, {s_uoff, s_roff, s_ulen, s_rlen, s_op, s_status}};
-        DevArr<uint8_t> arena;
-        DevGroup bytes{1 << 16, {arena}};
-        EchoLedger ledger() const { return EchoLedger{tab, (uint32_t)(tab_cap - 1), pool, (uint32_t)pool_cap, ctr}; }
-    } echo;
-
-    // ---- the pod and node reference directory (refs.hip, kwok_watch.h): namespace and name per pod
-    // slot, the per-call buffers of bind / lookup / read ----
-    struct KWOK_LOCAL Refs {
-        struct Bytes {
-            uint8_t b[KWOK_REF_STRIDE];
-        };
-        bool on = false;
-        DevArr<Bytes> pod_ref;            // [PLa] re-laid out with the pod arrays (grow_pods)
-        DevArr<uint16_t> pod_ref_len;     // [PLa]
-        DevArr<RefCounters> ctr;
-        Pinned<RefCounters> ctr_h;
-        // the stale guard: per kind (KWOK_KIND_*), bumped by every call that can create an object of it
-        uint64_t gen[2] = {0, 0};
-        // lookup / read: handles, sizes, offsets, slots, references, the scan's storage, the blob
-        DevArr<uint64_t> q_len, q_off;
-        DevArr<uint32_t> q_slot;
-        DevArr<kwok_ref> q_refs;
-        DevGroup items{4096, {q_len, q_off, q_slot, q_refs}};
-        DevArr<void> q_tmp;               // [tmp_bytes] (not zero-filled)
-        size_t tmp_bytes = 0;
-        DevArr<uint8_t> q_blob;
-        DevGroup blob{1 << 16, {q_blob}};
-        // bind: the spans (namespaces, then names), the handles (lookup's too) and the caller's arena
-        DevArr<uint64_t> b_off;
-        DevArr<uint32_t> b_len;
-        DevArr<int32_t> q_h;
-        DevGroup spans{4096, {{b_off, twice}, {b_len, twice}, q_h}};
-        DevArr<uint8_t> b_arena;
-        DevGroup arena{1 << 16, {b_arena}};
-        // the by-uid batch whose records the ingest is applying (null: an entry that carries no name)
-        const RefNote* note = nullptr;
-    } refs;
-    RefDir ref_dir() const {
-        return RefDir{reinterpret_cast<uint8_t*>(refs.pod_ref.p), refs.pod_ref_len, reinterpret_cast<const uint8_t*>(uid.pod_uid.p),
-                      uid.pod_uid_len, refs.ctr};
-    }
-
-    // ---- the pod codec on the GPU (json.hip): per-document buffers, the codec's
-    // selectors, the spec table (kwok_spec_key -> spec id) ----
-    struct KWOK_LOCAL Json {
-        DevArr<uint64_t> off;
-        DevArr<uint32_t> len;
-        DevArr<uint8_t> op;
-        DevArr<int32_t> handle;
-        DevArr<JsonPodSide> side;
-        DevArr<uint32_t> host_list;
-        DevArr<kwok_pod_event> fix_ev;     // the listed documents' records (gathered, completed, scattered)
-        DevArr<JsonPodSide> fix_side;
-        DevGroup docs{4096, {off, len, op, handle, side, host_list, fix_ev, fix_side}};
-        DevArr<uint32_t> n_host;           // [1]
-        Pinned<uint32_t> n_host_h;         // [1]
-        DevArr<JsonCfg> cfg;
-        Pinned<JsonCfg> cfg_h;             // staging
-        DevArr<uint64_t> tab_key;
-        DevArr<int32_t> tab_id;
-        DevArr<int32_t> nstat;             // node documents: the device decode's status per document
-        DevArr<kwok_node_event> nev_fix;   // node records gathered for / scattered from the host
-        DevGroup node_docs{4096, {nstat, nev_fix}};
-        DevArr<uint2> tab_canon;           // per slot: offset / length of its spec's canonical string in canon
-        DevArr<uint8_t> canon;             // the registered specs' canonical strings (json_spec_canon)
-        DevGroup canon_bytes{4096, {canon}};
-        uint32_t tab_mask = 0;
-        bool tab_dirty = true;
-    } json;
-    std::unordered_map<uint64_t, int32_t> spec_keys;  // kwok_spec_key -> spec id (-2: two specs share the key)
-    std::unordered_map<uint64_t, std::string> spec_canon;  // kwok_spec_key -> the canonical string of its spec
-
-    // ---- specs / blobs ----
-    std::unordered_map<std::string, int32_t> spec_ids;
-    uint32_t hb_len = HB_LEN, hb_stride = HB_STRIDE;  // heartbeat patch bytes / arena stride (16-aligned)
-    HeartbeatTemplate hb_tpl;     // the heartbeat template (default or compiled from Config.NodeHeartbeatTemplate)
-    bool custom_hb = false;
-    std::string hb_tpl_text;
-    bool custom_pod = false;      // Config.PodStatusTemplate in use (compiled per spec)
-    bool custom_node = false;     // Config.NodeInitializationTemplate in use (compiled per node status)
-    std::string pod_tpl, node_tpl, start_s;  // their texts; StartTime() (RFC3339 of start_time_unix)
-    std::unordered_map<std::string, uint64_t> node_tpl_blobs;  // node status fields -> compiled blob
-    std::vector<SpecDesc> specs_h;
-    std::string spec_bytes_h;
-    DevBuf<SpecDesc> d_specs;
-    DevBuf<uint8_t> d_spec_bytes;
-    std::vector<uint16_t> spec_nxt_h;  // timestamp lookups of every spec (build_ts_lookup)
-    DevBuf<uint16_t> d_spec_nxt;
-    DevBuf<uint8_t> d_unit_tab;      // k_emit's unit tables (16 bytes per unit), appended per spec
-    DevBuf<uint16_t> d_unit_desc;
-    uint32_t tab_units = 0;
-    uint32_t max_pod_len = 0;
-    std::unordered_map<std::string, uint64_t> blob_ids;
-    uint64_t empty_blob = 0;      // the blob of a node with an empty status (every status field absent)
-    std::atomic<bool> has_empty_blob{false};
-    std::string blob_h;
-    size_t blob_up_lo = SIZE_MAX;  // blob_h bytes from here on are not on the device yet (upload_blobs)
-    DevBuf<uint8_t> d_blob;
-    uint32_t max_init_len = 0;
-
-    // ---- tick ----
-    // A tick's outputs (header, lists, arena) live in one of two slots, so tick N+1
-    // can be queued while tick N is collected (kwok_tick_submit / _collect).  Slot 1
-    // is allocated on the first submit that finds slot 0 busy.
-    struct TickSlot {
-        TickHdr* hdr_h = nullptr;  // pinned: k_tick publishes the field totals here
-        uint8_t* arena = nullptr;
-        uint64_t arena_cap = 0;
-        int32_t *hb_nodes = nullptr, *init_nodes = nullptr, *pp_pods = nullptr, *del_pods = nullptr;
-        uint64_t *init_off = nullptr, *pp_off = nullptr;
-        uint32_t *init_len = nullptr, *pp_len = nullptr;
-        uint8_t* del_fin = nullptr;
-        DevState* d_S = nullptr;    // S with this slot's outputs, in device memory (out-of-line kernel phases)
-        DevState* S_pin = nullptr;  // pinned staging for its upload
-        DevState S_up{};            // the copy last uploaded
-        hipEvent_t done = nullptr;  // recorded after the tick's launches
-        hipEvent_t pev[8] = {};     // profiling: FRONT(+BACK) launch start/stop, BACK launch start/stop, k_emit,
-                                    // k_pod_jobs
-        uint4* pp_job = nullptr;    // k_tick -> k_emit job records
-        uint64_t* init_job = nullptr;
-        uint32_t* emit_n = nullptr;
-        bool emit_queued = false;   // k_emit was enqueued behind the tick's launches
-        bool split = false;         // TICK_SPLIT: k_pod_jobs builds the pod jobs after the tick's launches
-        bool fuse = false;          // ... and writes their patch bytes itself (DevState::fuse_pods)
-        bool inits_folded = false;  // ... and the node inits' too (no k_emit launch: KWOK_FOLD_INITS)
-        bool quiet = false;         // only pods with an event are Use-checked (kwok_engine::quiet)
-        bool once = false;          // launched as k_once / k_once_stream (a tick expected to have nothing to emit)
-        bool once_stream = false;   // ... as k_once_stream: the engine writes every heartbeat body
-        bool once_use = false;      // ... reading the per-bucket summaries (counted when it retires as a once tick)
-        hipEvent_t rd = nullptr;    // kwok_read_arena_async: the last read queued from this slot's arena
-        bool rd_pending = false;    //   (a submit or an arena growth that takes the slot waits for it)
-        bool no_once = false;       // k_once found work: the tick runs again with k_tick
-        bool alloc = false;
-        // What the heartbeat region [0, n x stride) of `arena` provably holds: n complete
-        // bodies of the template generation `gen` at `clock`.  Written by retire alone,
-        // for a tick that completed without error, was not skipped on the device or
-        // requeued, was not redone after k_once_stream found work and ran its stream; cleared by everything that
-        // replaces, poisons or is about to overwrite the arena (grow_arena, alloc_slot,
-        // every enqueue, so also a failed tick and the debug layout-fault tick) and by a
-        // template change.  A tick whose layout matches it exactly writes only the lines
-        // that differ from these bodies (hb_prev).
-        struct HbValid {
-            bool ok = false;
-            const uint8_t* arena = nullptr;
-            uint32_t n = 0, stride = 0, units = 0, gen = 0;
-            uint64_t clock = 0;
-        } hb_valid;
-        uint64_t hb_prev = 0;       // this tick's stream is a delta against the bodies of this clock (0: all bytes)
-        uint32_t hb_n = 0;          // bodies this tick's stream lays out
-        bool hb_record = false;     // retire may record this tick's bodies (not requeued, no layout fault, streamed)
-        // What `hb_nodes` provably holds: the n handles of a count of state generation gen.
-        // Follows HbValid: written by retire of a clean k_once_stream tick in this slot
-        // (counted, or reused: the list it found), cleared by every enqueue into the slot
-        // and by alloc_slot (the lists are allocated once).  A reused tick needs an exact match.
-        struct ListValid {
-            bool ok = false;
-            const int32_t* list = nullptr;
-            uint32_t n = 0;
-            uint64_t gen = 0;
-        } list_valid;
-        bool count_reused = false;  // launched as k_hb_stream: the count is the engine's clean-count record
-        bool requeued = false;      // the launch in flight is a requeue (the first one skipped, or the tick was redone)
-        uint64_t state_gen = 0;     // the engine's state generation at the tick's enqueue
-        // the tick in the slot
-        int state = 0;  // SLOT_FREE, SLOT_QUEUED (enqueued), SLOT_DONE (finished on the host, not collected)
-        uint64_t now = 0, target = 0;
-        uint32_t tag = 0;
-        uint32_t epoch = 0;         // heartbeat_epoch of the tick
-        uint64_t ref_gen[2] = {0, 0};  // the reference directory's counters at the tick's submit (kwok_read_refs)
-        int rc = 0;
-        std::string err;
-        kwok_tick_result res{};
-    };
-    TickSlot slots[2];
-    int queue[2] = {-1, -1};  // queued / done slots in submission order
-    int nq = 0;
-    int cur = -1;             // slot of the last collected tick (kwok_read_outputs)
-    size_t NLa = 0, PLa = 0;  // output list capacities
-    uint64_t arena_need = 0;  // worst-case output bytes of one tick
-    ListDesc* d_ld = nullptr;  // [W] or scratch
-    ncclComm_t comm = nullptr;
-    XMsg* d_xall = nullptr;
-    XMsg* h_xall = nullptr;  // pinned
-    uint32_t* d_xsend = nullptr;
-    uint32_t* d_xrecv = nullptr;
-    size_t xlist_cap = 0;
-    // TICK_XSPEC: after a tick whose lists were too long to be inline, the next
-    // ticks send their lists in a second allgather right behind the messages (no
-    // host round trip) with capacities from that tick's longest lists; every rank
-    // takes the same decisions (from the same gathered messages, in lockstep)
-    uint32_t xspec_u = 0, xspec_r = 0;  // capacities per rank (0: off)
-    uint32_t xspec_ttl = 0;             // ticks left
-    uint32_t xspec_alloc = 0;           // entries allocated per rank in d_ssend / d_srecv
-    uint32_t* d_ssend = nullptr;
-    uint32_t* d_srecv = nullptr;
-    int xspec_env = -1;                 // KWOK_XSPEC: 0 off, N: ticks kept on after a long-list tick (default 256)
-    uint64_t xspec_miss = 0;  // diagnostics: speculative ticks whose lists did not fit
-    uint32_t n_stream = 0;      // k_tick heartbeat streamer blocks (the chain blocks: S.n_chain)
-    uint32_t n_once_stream = 0; // k_once_stream's streamer blocks (512 threads each; KWOK_ONCE_STREAMERS), 0: by size
-    uint32_t emit_grid = 0;     // k_emit blocks
-    bool emit_hint = true;      // events were ingested since the last submit: the tick likely emits patches
-    bool sync_spin = true;      // spin on a tick's completion event (KWOK_SYNC=spin, the default)
-    bool chain_prio = false;    // KWOK_TICK_PRIO=1: s_setprio 3 on the chain blocks
-    bool no_stream = false;     // KWOK_TICK_NO_STREAM=1: diagnostics - heartbeat bodies not written
-    bool split_jobs = true;     // KWOK_SPLIT=0: pod jobs of event ticks in the chain blocks (A/B)
-    int fuse_emit = -1;         // KWOK_FUSE_EMIT: 1 always / 0 never fuse the pod bytes into k_pod_jobs; -1 dense ticks
-    bool sparse_jobs = true;    // unfused split ticks: k_sparse_jobs over FRONT's group records (KWOK_SPARSE_JOBS=0: off)
-    bool fold_inits = true;     // KWOK_FOLD_INITS=0: a fused tick's node inits by k_emit (A/B)
-    uint64_t pod_records_since_tick = 0;  // pod records ingested since the last tick was enqueued (fused emission)
-    uint32_t n_untabled = 0;    // registered specs without unit tables (no fused emission while any)
-    // Quiet ticks.  A tick's Use(podIP) of an evaluated pod (pod_controller.go:
-    // 378-382) is a no-op when the address is already in `used`.  Only a Put clears
-    // a bit, and Puts come from ingest (Deleted events), kwok_pool_put, and the
-    // deletions a tick makes of the pods marked at the ingest before it.  So after
-    // two submits with nothing in between, the previous tick Use-checked every
-    // evaluated pod and released nothing: this tick need only Use-check pods with
-    // an event (single rank; KWOK_QUIET=0 checks every pod).
-    // Also, while every in-CIDR podIP a live pod holds was assigned to it by this
-    // engine (no pod was created or updated with a podIP of its own, and no Deleted
-    // event released an address its pod did not hold: the GPU apply pass flags
-    // those, IngSummary::foreign), every such address has exactly one holder and
-    // stays in `used` until that holder is deleted: then no Use changes anything
-    // and the Use checks of pods without an event are skipped in every tick.
-    uint32_t quiet = 0;         // submits since the last ingest / pool_put / cni_assign
-    bool foreign_ips = false;   // sticky: a podIP not assigned by this engine entered the pool
-    bool global_foreign = false;  // multi rank, sticky: some rank's exchange message carried its foreign_ips
-    bool quiet_ok = true;
-    bool once_ok = true;        // KWOK_ONCE=0: quiet ticks always run k_tick (A/B)
-    bool once_stream_ok = true; // KWOK_ONCE_STREAM=0: ... those of engines that write every body (A/B; k_once stays)
-    // the last retired tick patched pods that took no address in it (created with an empty
-    // status: patched without IPs, their Gets follow in the next tick): that tick is not
-    // quiet, whatever the events say.  k_once_stream's prediction only: a redone tick
-    // writes its whole stream again, k_tick here writes the changed lines
-    bool pp_followup = false;
-    // k_once's per-bucket summaries (DevState::once_sum): valid while nothing has changed a
-    // pod state since the BUILD tick of generation sum_gen was enqueued (every ingest, CNI
-    // assignment, pool Put, zombie sweep and k_tick launch clears sum_valid)
-    bool once_sum_ok = true;    // KWOK_ONCE_SUM=0: every k_once tick reads the pod rows (A/B)
-    bool sum_valid = false;
-    uint32_t sum_gen = 0;
-    // Count reuse.  k_once_stream's count (handle list, totals) reads
-    // node and pod state words, pod_fill, hb_bpre and the managed count, never `now`: a
-    // quiet tick that follows a cleanly counted one with none of those changed in between
-    // would count the same again, so it launches the streamers alone (k_hb_stream) and
-    // retire fills its header from the record.  state_gen is bumped wherever sum_valid is
-    // cleared (every ingest, CNI assignment, pool Put, zombie sweep, redo and k_tick launch)
-    // and by every node / pod batch, pod capacity growth and template upload besides;
-    // resync sweeps change state through the ingest paths.  A tick records the generation
-    // it was enqueued under; a reused tick has no net that finds unexpected work, so the
-    // generation alone decides.
-    bool count_reuse_ok = true;  // KWOK_COUNT_REUSE=0: every quiet tick counts (A/B, tests)
-    uint64_t state_gen = 1;
-    void state_changed() {
-        sum_valid = false;
-        state_gen++;
-    }
-    // the last clean count: written by retire alone, for a k_once_stream tick that counted
-    // and completed without error, redo, device skip or requeue; tot is the device-written
-    // part of its header (before derive_header), gen the generation it was enqueued under
-    struct CleanCount {
-        bool ok = false;
-        uint64_t gen = 0;
-        uint64_t tot[16] = {};
-    } clean_count;
-    uint64_t stats[KWOK_STAT_COUNT] = {};  // kwok_engine_stats
-    uint8_t* dump_h = nullptr;  // kwok_dump_pods' page-locked staging
-    size_t dump_cap = 0;
-    bool ingest_zc = true;      // KWOK_INGEST_ZC=0: pod batches in kwok_host_alloc memory copied to HBM first
-    bool results_stream = true;   // KWOK_INGEST_RS=0: a chunked batch's results copied on the engine stream
-    bool results_kernel = false;  // KWOK_INGEST_RESULTS_KERNEL=1: pod batch results written into mapped host arrays by a kernel
-    double last_chunk_cut = 0.4;  // KWOK_INGEST_LAST_CUT: a chunked batch's last chunk is (1 - this) of the others
-    bool new_mapped = true;       // KWOK_INGEST_NEW_MAPPED=0: kwok_pod_rec12 create handles copied back, not written in place
-    bool hb_delta = true;       // KWOK_HB_DELTA=0: every tick writes the whole heartbeat stream (A/B, tests)
-    uint32_t hb_gen = 0;        // heartbeat template generation (bumped by every upload of the template or `start`)
-    int nt_env = -1;            // KWOK_HB_NT (0 / 1: heartbeat stores plain / non-temporal), else automatic
-    int share_env = -1;         // KWOK_TICK_STREAM_SHARE (/1024 of the stream to the streamer blocks), else automatic
-    uint32_t tick_tag = 0;      // nonzero id of the last FRONT launch
-    uint64_t front_launches = 0;  // FRONT launches since the cross-block state was last zeroed
-    // diagnostics
-    bool prof = false;
-    double prof_ms[KWOK_T_COUNT] = {};
-    uint64_t prof_ticks = 0;
-    double host_ms[KWOK_H_COUNT] = {};
-    // KWOK_TICK_TRACE=1: per-block phase stamps, summarised on stderr at destroy
-    std::vector<uint64_t> trace_h;
-    double trace_sum[TRACE_SLOTS + 2][3] = {};  // chain stamps, streamer entry / exit
-    uint64_t trace_ticks = 0, trace_seen = 0;
-    uint64_t host_ticks = 0;
-    // a failed tick leaves device and host state out of step: every later call
-    // fails with KWOK_EDEVICE (destroy and recreate the engine, re-ingest by List)
-    bool poisoned = false;
-    bool iprof = false;
-    WorkPool workers;  // host threads of the ingest partitions  // KWOK_INGEST_PROF=1: host ingest / retire phase times on stderr
-    uint32_t debug_fail_chunk = 0;  // KWOK_DEBUG_INGEST_FAIL_CHUNK=N: chunk N of a pod batch fails before its apply (tests)
-    uint32_t debug_fail_apply = 0;  // KWOK_DEBUG_INGEST_FAIL_APPLY=N: chunk N fails after its first apply pass (tests)
-    // the pod batch in progress changed the state (placeholder nodes, capacity, the
-    // apply pass): a failure from then on leaves the batch partly applied (poison)
-    bool ing_mutated = false;
-    uint32_t ing_chunk = 0;     // the chunk ingest_chunk works on (debug injection)
-    uint64_t debug_fault_tick = 0;  // KWOK_DEBUG_LAYOUT_FAULT_TICK=N: tick N gets a wrong heartbeat layout (tests)
-
-    int fail(int code, const char* fmt, ...) {
-        char b[512];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(b, sizeof b, fmt, ap);
-        va_end(ap);
-        err = b;
-        return code;
-    }
-    bool owns(uint32_t bucket) const { return bucket >= b_lo && bucket < b_hi; }
-    // pod handle <-> local slot (bucket_local * Cp + index)
-    int32_t pod_handle(uint32_t slot) const { return (int32_t)((b_lo + slot / Cp) * Hs + slot % Cp); }
-    // KWOK_OK (slot set), KWOK_ENOTMINE (another rank's bucket) or KWOK_ENOTFOUND
-    int pod_slot(int64_t h, uint32_t* slot) const {
-        if (h < 0 || h / Hs >= B) return KWOK_ENOTFOUND;
-        const uint32_t b = (uint32_t)(h / Hs), i = (uint32_t)(h % Hs);
-        if (!owns(b)) return KWOK_ENOTMINE;
-        if (i >= Cp) return KWOK_ENOTFOUND;
-        *slot = (b - b_lo) * Cp + i;
-        return KWOK_OK;
-    }
-};
-
-#define HIPCHK(e, x)                                                                              \
-    do {                                                                                          \
-        hipError_t _r = (x);                                                                      \
-        if (_r != hipSuccess) return (e)->fail(KWOK_EDEVICE, "%s: %s", #x, hipGetErrorString(_r)); \
-    } while (0)
 
 namespace {
 
@@ -723,47 +84,6 @@ const void* host_mapped(const void* p, size_t n) {
     const HostReg& r = it->second;
     if (!r.dev || a + n > it->first + r.len) return nullptr;
     return r.dev + (a - it->first);
-}
-
-template <class T>
-int dalloc(kwok_engine* e, T** p, size_t n) {
-    size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-    hipError_t r = hipMalloc((void**)p, bytes);
-    if (r != hipSuccess) return e->fail(KWOK_ENOMEM, "hipMalloc(%zu): %s", bytes, hipGetErrorString(r));
-    r = hipMemsetAsync(*p, 0, bytes, e->st);
-    if (r != hipSuccess) return e->fail(KWOK_EDEVICE, "hipMemset: %s", hipGetErrorString(r));
-    return KWOK_OK;
-}
-template <class T>
-void dfree(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
-// grow a device buffer to hold `bytes` (keeps contents)
-template <class T>
-int dgrow(kwok_engine* e, DevBuf<T>& b, size_t n) {
-    if (n <= b.n) return KWOK_OK;
-    size_t cap = std::max<size_t>(n, b.n * 2 + 64);
-    T* p = nullptr;
-    if (hipMalloc((void**)&p, cap * sizeof(T)) != hipSuccess) return e->fail(KWOK_ENOMEM, "grow %zu", cap * sizeof(T));
-    if (b.p) {
-        HIPCHK(e, hipMemcpyAsync(p, b.p, b.n * sizeof(T), hipMemcpyDeviceToDevice, e->st));
-        HIPCHK(e, hipStreamSynchronize(e->st));
-        (void)hipFree(b.p);
-    }
-    b.p = p;
-    b.n = cap;
-    return KWOK_OK;
-}
-
-template <class T>
-int dalloc(kwok_engine* e, DevArr<T>* a, size_t n) {
-    return dalloc(e, &a->p, n);
-}
-template <class T>
-void dfree(DevArr<T>& a) {
-    a.release();
 }
 
 }  // namespace
@@ -848,113 +168,16 @@ int upload_specs(kwok_engine* e) {
     return KWOK_OK;
 }
 
-int drain(kwok_engine* e);  // finish every queued tick on the host (below)
-int tick_submit_check(kwok_engine* e, int64_t now_unix);  // kwok_tick_submit's checks / the rest (below)
-int tick_submit_impl(kwok_engine* e, int64_t now_unix);
-int enqueue_tick(kwok_engine* e, int k, bool requeue);
+}  // namespace
+
+namespace kwok {
 int poisoned(kwok_engine* e) {
     return e->fail(KWOK_EDEVICE, "a failed tick left the engine out of step with the device: destroy it and "
                                  "recreate it (re-ingest by List)");
 }
+}  // namespace kwok
 
-// the output arena must hold the worst case of one tick.  It changes when the
-// capacity, the specs or the node blobs do (ingest, registration), and is
-// reserved then for the slots the next submit may take (a free slot whose outputs
-// the caller is not reading), not inside that tick: the 1M x 10M fleet's first
-// tick would otherwise reallocate ~8 GB (~0.7 ms of its enqueue).  A slot still
-// queued grows at its next submit.
-enum { SLOT_FREE = 0, SLOT_QUEUED = 1, SLOT_DONE = 2 };
-int grow_arena(kwok_engine* e, kwok_engine::TickSlot& T);
-int size_arena(kwok_engine* e) {
-    e->arena_need = (uint64_t)e->NL * e->hb_stride + (uint64_t)e->NL * ((e->max_init_len + 15u) & ~15u) +
-                    (uint64_t)e->PL * e->max_pod_len + 256;
-    for (int i = 0; i < 2; i++) {
-        kwok_engine::TickSlot& T = e->slots[i];
-        if (T.alloc && T.state == SLOT_FREE && i != e->cur)
-            if (int rc = grow_arena(e, T)) return rc;
-    }
-    return KWOK_OK;
-}
-int grow_arena(kwok_engine* e, kwok_engine::TickSlot& T) {  // T holds no queued tick
-    if (e->arena_need <= T.arena_cap) return KWOK_OK;
-    if (T.rd_pending) {  // (an asynchronous read of the old arena still in flight)
-        if (hipEventSynchronize(T.rd) != hipSuccess) return e->fail(KWOK_EDEVICE, "kwok_read_arena_async");
-        T.rd_pending = false;
-    }
-    const uint64_t need = std::max<uint64_t>(e->arena_need, T.arena_cap + T.arena_cap / 2);
-    if (T.arena) (void)hipFree(T.arena);
-    T.arena = nullptr;
-    T.arena_cap = 0;
-    T.hb_valid.ok = false;  // a new (possibly poisoned) arena holds no bodies
-    if (hipMalloc((void**)&T.arena, need) != hipSuccess) return e->fail(KWOK_ENOMEM, "arena %llu", (unsigned long long)need);
-    T.arena_cap = need;
-    if (getenv("KWOK_DEBUG_POISON"))  // diagnostics: bytes no kernel writes read as 0xEE, not as stale data
-        HIPCHK(e, hipMemsetAsync(T.arena, 0xEE, need, e->st));
-    return KWOK_OK;
-}
-int alloc_slot(kwok_engine* e, int k) {
-    kwok_engine::TickSlot& T = e->slots[k];
-    int rc = 0;
-    T.hb_valid.ok = false;
-    T.list_valid.ok = false;
-    if ((rc = dalloc(e, &T.hb_nodes, e->NLa)) || (rc = dalloc(e, &T.init_nodes, e->NLa)) ||
-        (rc = dalloc(e, &T.init_off, e->NLa)) || (rc = dalloc(e, &T.init_len, e->NLa)) ||
-        (rc = dalloc(e, &T.pp_pods, e->PLa)) || (rc = dalloc(e, &T.pp_off, e->PLa)) || (rc = dalloc(e, &T.pp_len, e->PLa)) ||
-        (rc = dalloc(e, &T.del_pods, e->PLa)) || (rc = dalloc(e, &T.del_fin, e->PLa)) || (rc = dalloc(e, &T.d_S, 1)) ||
-        (rc = dalloc(e, &T.pp_job, e->PLa)) || (rc = dalloc(e, &T.init_job, e->NLa)) || (rc = dalloc(e, &T.emit_n, 2)))
-        return rc;
-    // the header is coherent host memory written with system-scope stores, so the
-    // completion event needs no system-scope release (measured ~1.7 us per tick)
-    if (hipHostMalloc((void**)&T.hdr_h, sizeof(TickHdr), hipHostMallocCoherent) != hipSuccess ||
-        hipHostMalloc((void**)&T.S_pin, sizeof(DevState), hipHostMallocDefault) != hipSuccess)
-        return e->fail(KWOK_ENOMEM, "pinned tick header");
-    memset(T.hdr_h, 0, sizeof(TickHdr));
-    if (hipEventCreateWithFlags(&T.done, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess)
-        return e->fail(KWOK_EDEVICE, "event create");
-    for (auto& ev : T.pev)
-        if (e->prof && !ev) HIPCHK(e, hipEventCreate(&ev));
-    T.alloc = true;
-    return KWOK_OK;
-}
-void free_slot(kwok_engine::TickSlot& T) {
-    void* ptrs[] = {T.arena, T.hb_nodes, T.init_nodes, T.init_off, T.init_len, T.pp_pods,
-                    T.pp_off, T.pp_len, T.del_pods, T.del_fin, T.d_S, T.pp_job, T.init_job, T.emit_n};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (T.hdr_h) (void)hipHostFree(T.hdr_h);
-    if (T.S_pin) (void)hipHostFree(T.S_pin);
-    if (T.done) (void)hipEventDestroy(T.done);
-    if (T.rd) (void)hipEventDestroy(T.rd);
-    for (auto& ev : T.pev)
-        if (ev) (void)hipEventDestroy(ev);
-}
-// this slot's outputs into S (what launches read), uploaded to the slot's device copy if changed
-int bind_slot(kwok_engine* e, int k) {
-    kwok_engine::TickSlot& T = e->slots[k];
-    DevState& S = e->S;
-    S.arena = T.arena;
-    S.arena_cap = T.arena_cap;
-    S.hb_nodes = T.hb_nodes;
-    S.init_nodes = T.init_nodes;
-    S.init_off = T.init_off;
-    S.init_len = T.init_len;
-    S.pp_pods = T.pp_pods;
-    S.pp_off = T.pp_off;
-    S.pp_len = T.pp_len;
-    S.del_pods = T.del_pods;
-    S.del_fin = T.del_fin;
-    S.hdr_host = T.hdr_h;
-    S.self = T.d_S;
-    S.pp_job = T.pp_job;
-    S.init_job = T.init_job;
-    S.emit_n = T.emit_n;
-    if (memcmp(&T.S_up, &S, sizeof(DevState)) != 0) {  // pointers / sizes changed since the last upload
-        *T.S_pin = S;  // the slot's previous upload has completed (its tick was collected)
-        HIPCHK(e, hipMemcpyAsync(T.d_S, T.S_pin, sizeof(DevState), hipMemcpyHostToDevice, e->st));
-        T.S_up = S;
-    }
-    return KWOK_OK;
-}
+namespace {
 
 uint64_t intern_blob(kwok_engine* e, const NodeBlob& b, int* rc) {
     std::string key = b.pre + '\x01' + b.post;
@@ -974,15 +197,6 @@ uint64_t intern_blob(kwok_engine* e, const NodeBlob& b, int* rc) {
     e->max_init_len = std::max(e->max_init_len, ilen);
     e->blob_up_lo = std::min<size_t>(e->blob_up_lo, off);  // uploaded once per batch (upload_blobs)
     return word;
-}
-
-// Tick completion events skip the system-scope release (the tick header is
-// written with system-scope stores), so before a copy engine reads what the
-// kernels wrote, record an event that performs it: the kernels' dirty L2 lines
-// (per XCD, not coherent with the copy engine) are written back first.
-int release_for_host(kwok_engine* e) {
-    HIPCHK(e, hipEventRecord(e->fence, e->st));
-    return KWOK_OK;
 }
 
 // The blobs interned since the last upload -> the device copy (SRC_PAD_FRONT
@@ -1028,6 +242,9 @@ int parse_opt_ip(const char* arena, kwok_str s, uint32_t* ip) {
     return KWOK_OK;
 }
 
+}  // namespace
+
+namespace kwok {
 int exchange(kwok_engine* e, void* send, size_t bytes, void* recv) {
     if (e->comm) {
         ncclResult_t r = ncclAllGather(send, recv, bytes, ncclUint8, e->comm, e->st);
@@ -1044,6 +261,9 @@ int exchange(kwok_engine* e, void* send, size_t bytes, void* recv) {
     HIPCHK(e, hipMemcpyAsync(recv, hr.data(), bytes * e->W, hipMemcpyHostToDevice, e->st));
     return KWOK_OK;
 }
+}  // namespace kwok
+
+namespace {
 
 // Grow every bucket's pod capacity to new_cp (<= the handle stride): the device
 // pod arrays are re-laid out bucket by bucket (a bucket's pods keep their index,
@@ -2802,7 +2022,6 @@ int json_nodes_listed(kwok_engine* e, uint32_t nh, std::vector<uint32_t>& list) 
 }
 }  // namespace
 
-// ---- node documents on the GPU (json.hip k_json_nodes) -----------------------
 // kwok_ingest_nodes_json: WatchNodes / ListNodes from the documents themselves
 // (node_controller.go:206-279): decoded on the device, the host codec only for
 // the documents the scanner lists (a non-empty addresses / allocatable /
@@ -4472,754 +3691,6 @@ int kwok_pool_put(kwok_engine* e, const uint32_t* ips, size_t n) {
     e->state_changed();
     e->foreign_ips = true;  // releases of another rank's pods (multi rank)
     return flush_ops(e);
-}
-
-namespace {
-
-// k_emit for slot k's tick (S bound to slot k), behind its k_tick launch(es)
-int enqueue_emit(kwok_engine* e, int k) {
-    kwok_engine::TickSlot& T = e->slots[k];
-    if (e->prof) HIPCHK(e, hipEventRecord(T.pev[4], e->st));
-    launch_emit(e->S, e->emit_grid, T.now, (uint64_t)e->start, e->st);
-    HIPCHK(e, hipGetLastError());
-    if (e->prof) HIPCHK(e, hipEventRecord(T.pev[5], e->st));
-    T.emit_queued = true;
-    return KWOK_OK;
-}
-
-// Enqueue one tick on e->st into slot k.  Single rank: ONE persistent k_tick
-// launch (no host synchronisation, no graph needed).  Multi-rank: k_tick FRONT
-// (classify, bases, exchange message) -> allgather -> k_tick BACK (fold
-// messages, lists, pool, emission).  requeue: the slot's tick was skipped on
-// the device (queued behind a tick that needed finish_long_lists) and runs
-// again with its own tag and arrival target.
-int enqueue_tick(kwok_engine* e, int k, bool requeue) {
-    DevState& S = e->S;
-    kwok_engine::TickSlot& T = e->slots[k];
-    hipStream_t st = e->st;
-    // KWOK_INGEST_PROF: the host time to each launch of the tick (us after entry)
-    const auto q0 = clk::now();
-    double qs[4] = {-1, -1, -1, -1};  // hb_pre queued, slot bound, k_tick / k_once queued, k_pod_jobs queued
-    auto qstamp = [&](int i) { if (e->iprof) qs[i] = ms_between(q0, clk::now()) * 1e3; };
-    hipEvent_t* ev = e->prof ? T.pev : nullptr;
-    uint32_t nhb = (uint32_t)e->n_managed;  // = the device's count of managed local node slots
-    const bool fault_tick = e->debug_fault_tick && e->front_launches + 1 == e->debug_fault_tick && !requeue;
-    if (fault_tick) nhb++;  // tests: TICK_ERR_LAYOUT
-    // the delta stream: only when the slot's record says its arena holds exactly this
-    // tick's layout of bodies.  Multi-rank and heartbeat-once engines always write
-    // everything, and so does a requeued tick (its slot's first launch was skipped)
-    {
-        const kwok_engine::TickSlot::HbValid& V = T.hb_valid;
-        const bool can = e->hb_delta && !S.hb_once && !e->multi && !requeue && !fault_tick && !e->no_stream && V.ok &&
-                         V.arena == T.arena && V.n == nhb && V.stride == e->hb_stride && V.units == S.hb_units &&
-                         V.gen == e->hb_gen;
-        T.hb_prev = can ? V.clock : 0;
-        T.hb_n = nhb;
-        T.hb_record = !requeue && !fault_tick && !e->no_stream && !S.hb_once && !e->multi;
-        T.hb_valid.ok = false;  // the region is being rewritten: known again when this tick retires
-    }
-    T.requeued = requeue;
-    T.state_gen = e->state_gen;
-    if (e->hb_pre_dirty) {
-        // heartbeat handles are written in node order at per-chain-block bases:
-        // managed nodes of the buckets before each block's range (k_hb_pre, from
-        // the node batches' per-bucket counts)
-        launch_hb_pre(S, e->d_hb_pre, e->d_hb_bpre, st);
-        HIPCHK(e, hipGetLastError());
-        e->hb_pre_dirty = false;
-        qstamp(0);
-    }
-    // a long heartbeat stream is shared with the chain blocks once they are done
-    // (measured at C2: 921/1024 to the streamers; short streams: streamers only)
-    // a stream that fits the 256 MB Infinity Cache is rewritten from it every tick
-    // (plain stores); a larger one (1M nodes: 1.07 GB) is written non-temporally:
-    // 239 -> 216 us per 1M x 10M tick (no L2 pollution under the chain's reads,
-    // no dirty L2 left for the kernel-end write-back)
-    const uint64_t hb_bytes = (S.hb_once ? std::min<uint32_t>(nhb, 1u) : nhb) * (uint64_t)e->hb_stride;
-    S.hb_nt = e->nt_env >= 0 ? (uint32_t)e->nt_env : (hb_bytes >= (256ull << 20) ? 1u : 0u);
-    // (a delta tick's stores are whole 64-byte lines a quarter of a body apart: plain and
-    // non-temporal stores measured the same, tools/micro/fill_sparse.hip; the rule stays)
-    // the streamers' share: with the non-temporal stream the chain blocks finish
-    // sooner (1M x 10M: classification 172 -> 122 us) and take more of the tail
-    // (tools/share_sweep2.sh: 921 -> 860 /1024, 217 -> 208 us per tick)
-    // ticks that likely emit pod jobs (events since the last tick) build them in
-    // k_pod_jobs, one wave per two dirty 64-group runs, instead of the chain blocks'
-    // serial chunk walk (KWOK_SPLIT=0: the chain blocks, for A/B)
-    T.split = T.emit_queued && e->split_jobs;
-    // ... writing the pod patch bytes there too when every spec has unit tables
-    // (no 16-byte job record per patch written by k_pod_jobs and read back by k_emit)
-    // and the tick is dense: pod records ingested since the last tick (creates,
-    // updates, deletes: a bound on the patches their pods can need) >= 1/4 of the pod slots,
-    // so most dirty runs hold hundreds of jobs (1M x 10M initial tick: emission
-    // 1.79 -> 1.72 ms).  A sparse tick's runs hold a few jobs each; their serial
-    // emission per wave loses to k_emit's packed 64-job chunks (C4 churn tick
-    // 0.51 -> 0.57 ms fused; tools/gpu_r6b.sh)
-    if (!requeue) {  // (a requeued tick keeps its decision)
-        const bool dense = e->pod_records_since_tick * 4 >= (uint64_t)S.nb * e->Cp;
-        e->pod_records_since_tick = 0;
-        T.fuse = T.split && e->n_untabled == 0 && (e->fuse_emit > 0 || (e->fuse_emit < 0 && dense));
-    }
-    S.fuse_pods = T.fuse ? 1u : 0u;
-    S.sparse_jobs = T.split && !T.fuse && e->sparse_jobs ? 1u : 0u;
-    T.inits_folded = false;  // (set where k_pod_jobs is launched)
-    // ... and leave the whole stream to the streamers: a dirty chain block's share
-    // of it would hold up the pool phase, which waits for every dirty block
-    // a tick expected to have nothing to emit (no events since the previous tick, quiet
-    // Use checks) is counted by k_once: one wave per bucket, every load of the bucket in
-    // flight at once.  One that has work after all is run again with k_tick by retire
-    // (TickHdr::redo; a launch queued behind it skips).  A heartbeat-once engine's is
-    // k_once alone; an engine that writes every body runs k_once_stream, the same count
-    // beside the heartbeat streamers (KWOK_ONCE_STREAM=0: k_tick, for A/B)
-    if (!requeue) T.no_once = false;
-    T.once = !e->multi && e->once_ok && !T.emit_queued && !T.split && T.quiet && !T.no_once &&
-             S.cn <= (uint32_t)ONCE_NODE_LDS && e->PL < (1u << ONCE_FIELD_BITS) && e->NL < (1u << ONCE_FIELD_BITS) &&
-             (S.hb_once || (e->once_stream_ok && e->n_stream > 0 && !e->no_stream && !e->pp_followup));
-    T.once_stream = T.once && !S.hb_once;
-    // count reuse: the engine holds a clean count of this very state and the slot's handle list
-    // is that count's - the streamers alone (k_hb_stream); retire fills the header from the record
-    {
-        const kwok_engine::TickSlot::ListValid L = T.list_valid;
-        const kwok_engine::CleanCount& C = e->clean_count;
-        T.list_valid.ok = false;  // (whatever runs may write the list: known again when this tick retires)
-        T.count_reused = T.once_stream && !requeue && !fault_tick && e->count_reuse_ok && C.ok && C.gen == e->state_gen &&
-                         C.tot[AG_HB] == nhb && L.ok && L.list == T.hb_nodes && L.n == nhb && L.gen == e->state_gen;
-    }
-    // (k_once_stream's counting blocks are done in ~10 us: the stream is the streamers')
-    S.stream_share = e->n_stream == 0 ? 0u
-                     : T.count_reused  ? 1024u  // (nobody else to write a tail)
-                     : e->share_env >= 0 ? (uint32_t)e->share_env
-                                         : (hb_bytes < (32ull << 20) || T.split || T.hb_prev || T.once_stream ? 1024u
-                                            : S.hb_nt                                        ? 860u
-                                                                                             : 921u);
-    S.use_events_only = T.quiet ? 1u : 0u;
-    S.foreign = e->foreign_ips ? 1u : 0u;
-    int rc = bind_slot(e, k);
-    if (rc) return rc;
-    qstamp(1);
-    const int prof = (ev ? TICK_PROF : 0) | (e->chain_prio ? TICK_PRIO : 0) | (e->no_stream ? TICK_NOSTREAM : 0) |
-                     (T.split ? TICK_SPLIT : 0);
-    if (!requeue) {
-        memset(T.hdr_h, 0, sizeof(TickHdr));  // the slot's previous tick was collected
-        if (++e->tick_tag == 0) e->tick_tag = 1;
-        T.tag = e->tick_tag;
-        T.target = ++e->front_launches * S.n_chain;
-    }
-    const uint64_t now = T.now;
-    if (T.once) {
-        // per-bucket summaries: BUILD them on the first once tick after a change, USE them after
-        uint32_t mode = ONCE_SUM_OFF;
-        if (e->once_sum_ok && e->Cp <= 0xFFFFu) {
-            if (!e->sum_valid) {
-                if (++e->sum_gen == 0) e->sum_gen = 1;
-                e->sum_valid = true;
-                mode = ONCE_SUM_BUILD;
-            } else {
-                mode = ONCE_SUM_USE;
-            }
-        }
-        T.once_use = mode == ONCE_SUM_USE;
-        // k_once_stream's 512-thread streamer blocks: one per CU, two (16 streaming waves) for a
-        // region past the Infinity Cache (hb_nt's size).  1M x 10M: 0.1146 ms per step with one,
-        // 0.1088 with two; 100k x 1M: 0.0156 with one, 0.0177 with two (profiles/q1_layout_ab.txt)
-        const uint32_t n_os = e->n_once_stream ? e->n_once_stream : hb_bytes >= (256ull << 20) ? 2 * e->n_stream : e->n_stream;
-        if (T.count_reused)
-            launch_hb_stream(S, n_os, now, (uint64_t)e->start, nhb, prof & (TICK_PROF | TICK_NOSTREAM), T.hb_prev, st,
-                             ev ? ev[0] : nullptr, ev ? ev[1] : nullptr);
-        else if (T.once_stream)
-            launch_tick_once_stream(S, n_os, now, (uint64_t)e->start, nhb, prof & (TICK_PROF | TICK_NOSTREAM), mode,
-                                    e->sum_gen, T.hb_prev, st, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr);
-        else
-            launch_tick_once(S, now, (uint64_t)e->start, nhb, prof & TICK_PROF, mode, e->sum_gen, st, ev ? ev[0] : nullptr,
-                             ev ? ev[1] : nullptr);
-        HIPCHK(e, hipGetLastError());
-        qstamp(2);
-    } else if (!e->multi) {
-        e->state_changed();  // (a k_tick may change pod states)
-        launch_tick(S, e->n_stream, now, (uint64_t)e->start, nhb, TICK_FRONT | TICK_BACK | prof, T.tag, T.target, st,
-                    ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, T.hb_prev);
-        HIPCHK(e, hipGetLastError());
-        qstamp(2);
-    } else {
-        e->state_changed();
-        launch_tick(S, e->n_stream, now, (uint64_t)e->start, nhb, TICK_FRONT | prof, T.tag, T.target, st,
-                    ev ? ev[0] : nullptr, ev ? ev[1] : nullptr);
-        // one allgather of the fixed-size exchange message, then BACK: it folds the
-        // gathered messages and applies the inline lists itself (no host round trip).
-        // Lists too long to be inline: BACK flags it and the host finishes the tick
-        // with a second allgather (finish_long_lists).
-        // After a long-list tick (TICK_XSPEC): the lists follow in a second allgather
-        // of fixed capacity and k_pool_apply_spec applies them if every rank's fit.
-        if (!requeue && e->xspec_ttl && --e->xspec_ttl == 0) e->xspec_u = e->xspec_r = 0;
-        const bool spec = e->xspec_u + e->xspec_r != 0;
-        if (spec) {
-            S.xcap_u = e->xspec_u, S.xcap_r = e->xspec_r;
-            launch_gather_lists(S, e->d_ssend, st, S.xcap_u, S.xcap_u, S.xcap_r);
-            HIPCHK(e, hipGetLastError());
-        }
-        rc = exchange(e, S.xmsg, sizeof(XMsg), e->d_xall);
-        if (rc) return rc;
-        if (e->XW > e->W) launch_emulate_msgs(S, e->d_xall, (uint32_t)e->XW, st);  // (diagnostics: one rank, XW > 1)
-        if (spec) {
-            const uint32_t per = S.xcap_u + S.xcap_r;
-            if ((rc = exchange(e, e->d_ssend, (size_t)per * 4, e->d_srecv))) return rc;
-            if (e->XW > e->W) launch_emulate_lists(S, e->d_srecv, per, (uint32_t)e->XW, per, st);  // (diagnostics)
-            launch_pool_apply_spec(S, e->d_srecv, st);
-            HIPCHK(e, hipGetLastError());
-        }
-        launch_tick(S, e->n_stream, now, (uint64_t)e->start, nhb, TICK_BACK | prof | (spec ? TICK_XSPEC : 0), T.tag,
-                    T.target, st, ev ? ev[2] : nullptr, ev ? ev[3] : nullptr);
-        HIPCHK(e, hipGetLastError());
-    }
-    // a fused launch writes the node inits too (its last blocks): no k_emit
-    T.inits_folded = T.fuse && e->fold_inits;
-    if (T.split) {
-        launch_pod_jobs(S, T.tag, st, T.inits_folded ? e->emit_grid : 0u, now, (uint64_t)e->start, ev ? ev[6] : nullptr,
-                        ev ? ev[7] : nullptr);
-        HIPCHK(e, hipGetLastError());
-        qstamp(3);
-    }
-    // the patch bytes, when events since the last tick make jobs likely (otherwise
-    // retire launches k_emit if the tick turns out to have jobs)
-    if (T.emit_queued && !T.inits_folded && (rc = enqueue_emit(e, k))) return rc;
-    HIPCHK(e, hipEventRecord(T.done, st));
-    if (e->iprof)
-        fprintf(stderr, "[kwok enqueue] us: hb_pre %.1f, bound %.1f, tick %.1f, pod_jobs %.1f, all %.1f\n", qs[0], qs[1], qs[2],
-                qs[3], ms_between(q0, clk::now()) * 1e3);
-    return KWOK_OK;
-}
-// multi rank, after the BACK launch of slot k's tick found lists too long to be
-// inline (the same on every rank: the flag comes from the gathered messages):
-// gather the lists, apply every rank's Uses and Puts, and run BACK again.  A tick
-// queued behind it skipped on the device (GridBar::skip) and is enqueued again.
-int finish_long_lists(kwok_engine* e, int k, int next) {
-    DevState& S = e->S;
-    kwok_engine::TickSlot& T = e->slots[k];
-    hipStream_t st = e->st;
-    T.hdr_h->xovf = 0;
-    // the skipped tick's allgather re-gathered the same messages (its FRONT did not run)
-    if (int rc = release_for_host(e)) return rc;
-    HIPCHK(e, hipStreamSynchronize(st));
-    HIPCHK(e, hipMemcpyAsync(e->h_xall, e->d_xall, sizeof(XMsg) * e->XW, hipMemcpyDeviceToHost, st));
-    HIPCHK(e, hipStreamSynchronize(st));
-    uint64_t maxl = 0, mu = 0, mr = 0;
-    for (int r = 0; r < e->XW; r++) {
-        maxl = std::max<uint64_t>(maxl, e->h_xall[r].n_use + e->h_xall[r].n_rel);
-        mu = std::max<uint64_t>(mu, e->h_xall[r].n_use);
-        mr = std::max<uint64_t>(mr, e->h_xall[r].n_rel);
-    }
-    if (e->xspec_env != 0) {
-        // the next ticks' speculative list exchange: room for 1.25x this tick's
-        // longest lists (the same on every rank: the gathered messages)
-        if (e->xspec_u + e->xspec_r) e->xspec_miss++;
-        auto cap = [](uint64_t m) { return (uint32_t)std::min<uint64_t>(((m + m / 4) | 1023) + 1, 1u << 30); };
-        const bool miss = e->xspec_u + e->xspec_r != 0;  // a speculative tick whose lists did not fit: grow
-        const uint32_t cu = miss ? std::max(e->xspec_u, cap(mu)) : cap(mu), cr = miss ? std::max(e->xspec_r, cap(mr)) : cap(mr);
-        if (cu + cr > e->xspec_alloc) {
-            if (e->d_ssend) (void)hipFree(e->d_ssend);
-            if (e->d_srecv) (void)hipFree(e->d_srecv);
-            e->d_ssend = e->d_srecv = nullptr;
-            e->xspec_alloc = 0;
-            if (hipMalloc((void**)&e->d_ssend, (size_t)(cu + cr) * 4) != hipSuccess ||
-                hipMalloc((void**)&e->d_srecv, (size_t)(cu + cr) * 4 * e->XW) != hipSuccess)
-                return e->fail(KWOK_ENOMEM, "speculative exchange lists");
-            e->xspec_alloc = cu + cr;
-        }
-        e->xspec_u = cu, e->xspec_r = cr;
-        e->xspec_ttl = e->xspec_env > 0 ? (uint32_t)e->xspec_env : 256u;
-    }
-    if (maxl > e->xlist_cap) {
-        if (e->d_xsend) (void)hipFree(e->d_xsend);
-        if (e->d_xrecv) (void)hipFree(e->d_xrecv);
-        e->xlist_cap = maxl;
-        if (hipMalloc((void**)&e->d_xsend, maxl * 4) != hipSuccess ||
-            hipMalloc((void**)&e->d_xrecv, maxl * 4 * e->XW) != hipSuccess)
-            return e->fail(KWOK_ENOMEM, "exchange lists");
-    }
-    int rc = bind_slot(e, k);
-    if (rc) return rc;
-    S.fuse_pods = T.fuse ? 1u : 0u;
-    S.sparse_jobs = T.split && !T.fuse && e->sparse_jobs ? 1u : 0u;
-    HIPCHK(e, hipMemsetAsync(&S.bar->skip, 0, sizeof(uint32_t), st));
-    const XMsg& me = e->h_xall[e->rank];
-    if (me.n_use + me.n_rel) {  // the chain blocks' list segments, gathered in block order
-        launch_gather_lists(S, e->d_xsend, st);
-        HIPCHK(e, hipGetLastError());
-    }
-    rc = exchange(e, e->d_xsend, maxl * 4, e->d_xrecv);
-    if (rc) return rc;
-    if (e->XW > e->W)  // (diagnostics)
-        launch_emulate_lists(S, e->d_xrecv, maxl, (uint32_t)e->XW, (uint32_t)(me.n_use + me.n_rel), st);
-    std::vector<ListDesc> ld(e->XW);
-    for (int r = 0; r < e->XW; r++) {
-        ld[r].use = e->d_xrecv + (size_t)r * maxl;
-        ld[r].rel = e->d_xrecv + (size_t)r * maxl + e->h_xall[r].n_use;
-        ld[r].n_use = (uint32_t)e->h_xall[r].n_use;
-        ld[r].n_rel = (uint32_t)e->h_xall[r].n_rel;
-    }
-    HIPCHK(e, hipMemcpyAsync(e->d_ld, ld.data(), sizeof(ListDesc) * e->XW, hipMemcpyHostToDevice, st));
-    launch_pool_apply(S, e->d_ld, e->XW, (uint32_t)maxl, st);  // every rank's Uses, then Puts pending
-    launch_tick(S, e->n_stream, T.now, (uint64_t)e->start, (uint32_t)e->n_managed,
-                TICK_BACK | TICK_XLISTS | (T.split ? TICK_SPLIT : 0), T.tag, T.target, st);
-    HIPCHK(e, hipGetLastError());
-    T.inits_folded = T.fuse && e->fold_inits;
-    if (T.split) {
-        launch_pod_jobs(S, T.tag, st, T.inits_folded ? e->emit_grid : 0u, T.now, (uint64_t)e->start);
-        HIPCHK(e, hipGetLastError());
-    }
-    if (T.inits_folded) T.emit_queued = true;  // (the fused launch wrote every patch)
-    else if ((rc = enqueue_emit(e, k))) return rc;  // this launch built the jobs
-    HIPCHK(e, hipStreamSynchronize(st));
-    if (next >= 0) return enqueue_tick(e, next, true);
-    return KWOK_OK;
-}
-
-// single rank: the kernel publishes the tick's field totals (TickHdr::tot); the
-// counts, output layout and counters follow from them
-void derive_header(TickHdr& H, uint64_t arena_cap, uint32_t hb_stride, bool hb_once) {
-    const uint64_t* t = H.tot;
-    H.n_hb = (uint32_t)t[AG_HB];
-    H.n_init = (uint32_t)t[AG_INIT];
-    H.n_pp = (uint32_t)t[AG_PP];
-    H.n_del = (uint32_t)t[AG_DEL];
-    H.n_use = 0;
-    H.n_rel = (uint32_t)t[AG_REL];
-    H.n_alloc_local = (uint32_t)t[AG_ALLOC];
-    H.n_eval = (uint32_t)t[AG_EVAL];
-    H.n_lock = (uint32_t)t[AG_LOCK];
-    H.init_bytes = t[AG_INIT_BYTES];
-    H.pp_bytes = t[AG_PP_BYTES];
-    H.hb_base = 0;
-    H.init_base = (uint64_t)(hb_once ? std::min<uint32_t>(H.n_hb, 1u) : H.n_hb) * hb_stride;
-    H.pod_base = H.init_base + H.init_bytes;
-    H.arena_bytes = H.pod_base + H.pp_bytes;
-    H.overflow = H.arena_bytes > arena_cap;
-    const int map[13] = {AG_HB, AG_INIT, AG_PP, AG_DEL, AG_ALLOC, AG_REL, AG_EVAL,
-                         AG_LOCK, AG_MANAGED, AG_READY, AG_TOTAL, AG_PENDING, AG_RUNNING};
-    for (int k = 0; k < 16; k++) H.local_counters[k] = H.counters[k] = k < 13 ? t[map[k]] : 0;
-    H.alloc_total = t[AG_ALLOC];
-    H.alloc_base = 0;
-    H.rel_total = t[AG_REL];
-}
-
-bool trace_enabled(const kwok_engine* e) { return e->S.trace != nullptr; }
-
-// KWOK_JOBS_TRACE=file: the k_pod_jobs wave stamps of the last tick with pod jobs
-// (tools/jobs_trace.py reads them), zeroed for the next
-void jobs_trace_dump(kwok_engine* e) {
-    const size_t n = (size_t)e->S.n_chain * (MAX_WC + 4) * 4;
-    std::vector<uint64_t> h(n);
-    if (hipMemcpy(h.data(), e->S.jtrace, n * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemset(e->S.jtrace, 0, n * 8) != hipSuccess)
-        return;
-    if (FILE* f = fopen(getenv("KWOK_JOBS_TRACE"), "wb")) {
-        fwrite(h.data(), 8, n, f);
-        fclose(f);
-    }
-}
-
-// per stamp k: earliest / median / latest block, microseconds after the earliest block start
-void trace_tick(kwok_engine* e) {
-    // (the rows allocated: k_once_stream and k_hb_stream run up to two streamer blocks per CU)
-    const size_t G = e->S.n_chain, N = G + std::max(2 * e->n_stream, e->n_once_stream);
-    static const int skip = getenv("KWOK_TICK_TRACE_SKIP") ? atoi(getenv("KWOK_TICK_TRACE_SKIP")) : 5;
-    static const uint64_t only = getenv("KWOK_TICK_TRACE_COUNT") ? strtoull(getenv("KWOK_TICK_TRACE_COUNT"), nullptr, 10) : 0;
-    if ((int)++e->trace_seen <= skip) {  // skip the initial (bulk) ticks; their stamps go (not every kernel writes every row)
-        (void)hipMemsetAsync(e->S.trace, 0, N * TRACE_SLOTS * 8, e->st);
-        return;
-    }
-    if (only && e->trace_ticks >= only) return;  // KWOK_TICK_TRACE_COUNT: summarise only the first traced ticks
-    const size_t TS = TRACE_SLOTS;
-    e->trace_h.assign(N * TS, 0);
-    if (release_for_host(e) || hipMemcpyAsync(e->trace_h.data(), e->S.trace, N * TS * 8, hipMemcpyDeviceToHost, e->st) != hipSuccess ||
-        hipMemsetAsync(e->S.trace, 0, N * TS * 8, e->st) != hipSuccess || hipStreamSynchronize(e->st) != hipSuccess)
-        return;
-    uint64_t t0 = ~0ull;
-    for (size_t b = 0; b < G; b++) t0 = std::min(t0, e->trace_h[b * TS]);
-    if (t0 == 0) {  // no chain or counting block ran (k_hb_stream): after the first streamer's start
-        t0 = ~0ull;
-        for (size_t b = G; b < N; b++)
-            if (e->trace_h[b * TS]) t0 = std::min(t0, e->trace_h[b * TS]);
-    }
-    // stamps a block did not reach this tick (a clean block skips the pool phase) are 0
-    auto summarise = [&](size_t lo, size_t hi, int k, double* out) {
-        std::vector<double> v;
-        for (size_t b = lo; b < hi; b++)
-            if (e->trace_h[b * TS + k] >= t0) v.push_back((double)(e->trace_h[b * TS + k] - t0) * 0.01);
-        if (v.empty()) return;
-        std::sort(v.begin(), v.end());
-        out[0] += v[0];
-        out[1] += v[v.size() / 2];
-        out[2] += v[v.size() - 1];
-    };
-    for (int k = 0; k < TRACE_SLOTS; k++) summarise(0, G, k, e->trace_sum[k]);
-    summarise(G, N, 0, e->trace_sum[TRACE_SLOTS]);
-    summarise(G, N, 6, e->trace_sum[TRACE_SLOTS + 1]);
-    if (getenv("KWOK_TICK_TRACE_SLOW")) {  // per XCC: median / max pods-done and arrival; the slowest blocks
-        std::vector<double> pd[16], ar[16];
-        std::vector<std::pair<double, size_t>> slow;
-        for (size_t b = 0; b < G; b++) {
-            const uint64_t* T = &e->trace_h[b * TS];
-            if (T[2] < t0 || T[3] < t0) continue;
-            const uint32_t x = (uint32_t)(T[21] >> 28) & 15u;
-            pd[x].push_back((double)(T[2] - t0) * 0.01);
-            ar[x].push_back((double)(T[3] - t0) * 0.01);
-            slow.emplace_back((double)(T[3] - t0) * 0.01, b);
-        }
-        for (int x = 0; x < 16; x++) {
-            if (pd[x].empty()) continue;
-            std::sort(pd[x].begin(), pd[x].end());
-            std::sort(ar[x].begin(), ar[x].end());
-            fprintf(stderr, "[kwok trace xcc %d] blocks %zu pods-done %.1f / %.1f arrived %.1f / %.1f\n", x, pd[x].size(),
-                    pd[x][pd[x].size() / 2], pd[x].back(), ar[x][ar[x].size() / 2], ar[x].back());
-        }
-        std::sort(slow.rbegin(), slow.rend());
-        for (size_t q = 0; q < std::min<size_t>(8, slow.size()); q++) {
-            const uint64_t* T = &e->trace_h[slow[q].second * TS];
-            fprintf(stderr, "[kwok trace slow] block %zu hw %08llx nodes %.1f pods %.1f sum %.1f drained %.1f arrived %.1f\n",
-                    slow[q].second, (unsigned long long)T[21], (double)(T[1] - t0) * 0.01, (double)(T[2] - t0) * 0.01,
-                    (double)(T[10] - t0) * 0.01, (double)(T[11] - t0) * 0.01, (double)(T[3] - t0) * 0.01);
-        }
-    }
-    if (getenv("KWOK_TICK_TRACE_RAW")) {  // the last block's 16 stamps (ad-hoc kernel probes), us after t0
-        fprintf(stderr, "[kwok trace raw]");
-        for (size_t k = 0; k < TS; k++) {
-            const uint64_t v = e->trace_h[(N - 1) * TS + k];
-            fprintf(stderr, " %.3f", k == 8 ? (double)v : v >= t0 ? (double)(v - t0) * 0.01 : -1.0);
-        }
-        fprintf(stderr, "\n");
-    }
-    e->trace_ticks++;
-}
-
-
-
-// k_once met work to emit in slot k's tick (a delete, patch, Get, Put, Use, pod
-// event or node init): run the tick again with k_tick (same tag and arrival
-// target: k_once made no arrivals).  The launch queued behind it skipped on the
-// device (GridBar::skip); retire enqueues it again afterwards.
-int redo_tick(kwok_engine* e, int k) {
-    kwok_engine::TickSlot& T = e->slots[k];
-    e->stats[KWOK_STAT_ONCE_REDO]++;
-    e->state_changed();
-    memset(T.hdr_h, 0, sizeof(TickHdr));
-    HIPCHK(e, hipMemsetAsync(&e->S.bar->skip, 0, sizeof(uint32_t), e->st));
-    T.no_once = true;
-    if (int rc = enqueue_tick(e, k, true)) return rc;
-    HIPCHK(e, hipEventSynchronize(T.done));
-    return KWOK_OK;
-}
-
-// Finish the oldest queued tick on the host: wait for it, complete a multi-rank
-// tick with long lists, derive the header, check errors, mirror DeletePods into
-// the host slot state.  The result stays in the slot until kwok_tick_collect.
-int retire(kwok_engine* e) {
-    int qi = -1;
-    for (int i = 0; i < e->nq; i++)
-        if (e->slots[e->queue[i]].state == SLOT_QUEUED) {
-            qi = i;
-            break;
-        }
-    if (qi < 0) return KWOK_OK;
-    const int k = e->queue[qi];
-    const int next = qi + 1 < e->nq ? e->queue[qi + 1] : -1;  // a tick queued behind this one
-    kwok_engine::TickSlot& T = e->slots[k];
-    T.state = SLOT_DONE;
-    T.rc = KWOK_OK;
-    // every failure here leaves the device state (advanced by the kernels) and the
-    // host mirrors / the caller's view out of step: the engine is poisoned, and a
-    // tick queued behind this one (it ran on that state) fails with it
-    auto failed = [&](int rc) {
-        T.rc = rc;
-        T.err = e->err;
-        e->poisoned = true;
-        if (next >= 0 && e->slots[next].state == SLOT_QUEUED) {
-            kwok_engine::TickSlot& U = e->slots[next];
-            (void)hipStreamSynchronize(e->st);
-            U.state = SLOT_DONE;
-            U.rc = rc;
-            U.err = e->err;
-        }
-        return rc;
-    };
-    const auto t1 = clk::now();
-    if (e->sync_spin) {
-        // spin on the tick's completion event: a blocking wait sleeps and pays the
-        // wake-up latency on every tick
-        hipError_t q;
-        while ((q = hipEventQuery(T.done)) == hipErrorNotReady) {
-        }
-        if (q != hipSuccess) return failed(e->fail(KWOK_EDEVICE, "tick: %s", hipGetErrorString(q)));
-    } else if (hipEventSynchronize(T.done) != hipSuccess) {
-        return failed(e->fail(KWOK_EDEVICE, "tick event sync"));
-    }
-    if (e->multi && T.hdr_h->xovf) {
-        int rc = finish_long_lists(e, k, next);
-        if (rc) return failed(rc);
-    }
-    if (e->multi && T.hdr_h->xforeign) e->global_foreign = true;  // (the BACK launch that ran to the end)
-    bool requeue_next = false;
-    // a reused count: the totals the clean count published (k_hb_stream writes no header;
-    // a launch that skipped on the device was enqueued again as a counting tick)
-    if (T.count_reused) memcpy(T.hdr_h->tot, e->clean_count.tot, sizeof(T.hdr_h->tot));
-    if (T.once && T.hdr_h->redo) {
-        if (int rc = redo_tick(e, k)) return failed(rc);
-        requeue_next = next >= 0 && e->slots[next].state == SLOT_QUEUED;
-    }
-    const auto t2 = clk::now();
-    if (!e->multi) derive_header(*T.hdr_h, T.arena_cap, e->hb_stride, e->S.hb_once != 0);
-    const TickHdr& H = *T.hdr_h;
-    if (!H.err && (H.n_pp || H.n_init) && !T.emit_queued) {
-        // jobs nobody expected (no events since the previous tick): their bytes now
-        int rc = bind_slot(e, k);
-        if (!rc) rc = enqueue_emit(e, k);
-        if (rc) return failed(rc);
-        if (hipEventRecord(T.done, e->st) != hipSuccess || hipEventSynchronize(T.done) != hipSuccess)
-            return failed(e->fail(KWOK_EDEVICE, "k_emit"));
-    }
-    if (trace_enabled(e)) trace_tick(e);
-    if (e->S.jtrace && H.n_pp) jobs_trace_dump(e);
-    if (H.err) {
-        const uint32_t err = H.err;
-        // a tick queued behind a failed one ran on its state: fail it as well
-        (void)hipStreamSynchronize(e->st);
-        (void)hipMemsetAsync(e->S.bar, 0, sizeof(GridBar), e->st);  // the next tick starts from a clean count
-        (void)hipStreamSynchronize(e->st);
-        e->front_launches = 0;
-        int rc = (err & TICK_ERR_BARRIER)
-                     ? e->fail(KWOK_EDEVICE, "k_tick cross-block wait timed out (%u chain blocks not co-resident?)",
-                               e->S.n_chain)
-                 : (err & TICK_ERR_SEQ)
-                     ? e->fail(KWOK_ECOMM, "ranks out of step: the gathered exchange messages are of different ticks")
-                 : (err & TICK_ERR_EMIT)
-                     ? e->fail(KWOK_EDEVICE, "k_pod_jobs: a pod spec without unit tables in a fused emission")
-                     : e->fail(KWOK_EDEVICE, "k_tick: device heartbeat count differs from the host's (%llu)",
-                               (unsigned long long)e->n_managed);
-        e->poisoned = true;
-        if (next >= 0) {
-            kwok_engine::TickSlot& U = e->slots[next];
-            U.state = SLOT_DONE;
-            U.rc = rc;
-            U.err = e->err;
-        }
-        return failed(rc);
-    }
-    if (e->prof) {
-        // kernel time from the launch events; the phase split from the kernel's
-        // s_memrealtime stamps (100 MHz)
-        float k0 = 0, k1 = 0;
-        (void)hipEventElapsedTime(&k0, T.pev[0], T.pev[1]);
-        if (e->multi) (void)hipEventElapsedTime(&k1, T.pev[2], T.pev[3]);
-        float k2 = 0;
-        if (T.emit_queued && !T.inits_folded) (void)hipEventElapsedTime(&k2, T.pev[4], T.pev[5]);
-        float k3 = 0;
-        if (T.split) (void)hipEventElapsedTime(&k3, T.pev[6], T.pev[7]);
-        const double kern = (double)k0 + k1 + k2 + k3;
-        // the streamers' latest exit, kept on the device (they never touch the header)
-        unsigned long long send = 0;
-        (void)release_for_host(e);
-        (void)hipMemcpyAsync(&send, &e->S.bar->stream_end_max, 8, hipMemcpyDeviceToHost, e->st);
-        (void)hipMemsetAsync(&e->S.bar->stream_end_max, 0, 8, e->st);
-        unsigned long long nent = 0;  // (k_hb_stream: no counting block publishes the earliest entry)
-        if (T.count_reused) {
-            (void)hipMemcpyAsync(&nent, &e->S.bar->neg_entry_max, 8, hipMemcpyDeviceToHost, e->st);
-            (void)hipMemsetAsync(&e->S.bar->neg_entry_max, 0, 8, e->st);
-        }
-        (void)hipStreamSynchronize(e->st);
-        T.hdr_h->clk[CLK_STREAM_END] = send;
-        if (T.count_reused) T.hdr_h->clk[CLK_ENTRY_MIN] = ~nent;
-        auto span = [&](int a, int b) { return H.clk[b] > H.clk[a] ? (double)(H.clk[b] - H.clk[a]) * 1e-5 : 0.0; };
-        const double classify = span(CLK_ENTRY_MIN, CLK_P1_MAX), stream = span(CLK_ENTRY_MIN, CLK_STREAM_END);
-        const double header = span(CLK_P1_MAX, CLK_HDR), pool = span(CLK_BACK, CLK_POOL);
-        e->prof_ms[KWOK_T_CLASSIFY] += classify;
-        e->prof_ms[KWOK_T_STREAM] += stream;
-        e->prof_ms[KWOK_T_HEADER] += header;
-        e->prof_ms[KWOK_T_EXCHANGE] += e->multi ? span(CLK_HDR, CLK_BACK) : 0.0;
-        e->prof_ms[KWOK_T_POOL] += pool;
-        // what follows the header in the chain (pool, job lists) beyond the stream, and k_emit
-        e->prof_ms[KWOK_T_EMIT] += std::max(0.0, k0 + k1 - std::max(classify + header + pool, stream)) + k2 + k3;
-        e->prof_ms[KWOK_T_KERNEL] += kern;
-        e->prof_ms[KWOK_T_EMIT_KERNEL] += k2 + k3;  // k_emit and k_pod_jobs (split ticks)
-        e->prof_ticks++;
-    }
-    if (H.overflow) return failed(e->fail(KWOK_ENOMEM, "output arena overflow (%llu bytes)", (unsigned long long)H.arena_bytes));
-    // deleted nodes (and placeholders) whose last pod this tick deleted: their
-    // entries go (k_free_zombies, queued on the engine stream: a tick already
-    // queued behind this one reads no such node; every ingest follows it)
-    if (H.n_del) {
-        e->state_changed();
-        launch_free_zombies(e->S, e->st);
-        if (hipGetLastError() != hipSuccess) return failed(e->fail(KWOK_EDEVICE, "k_free_zombies"));
-    }
-    kwok_tick_result& r = T.res;
-    memset(&r, 0, sizeof(r));
-    r.n_heartbeat = H.n_hb;
-    r.heartbeat_len = e->hb_len;
-    r.heartbeat_stride = e->S.hb_once ? 0 : e->hb_stride;
-    r.n_node_init = H.n_init;
-    r.n_pod_patch = H.n_pp;
-    r.n_delete = H.n_del;
-    r.heartbeat_epoch = T.epoch;
-    r.arena_bytes = H.arena_bytes;
-    for (int c = 0; c < KWOK_COUNTER_COUNT; c++) {
-        r.counters[c] = H.counters[c];
-        r.local_counters[c] = H.local_counters[c];
-    }
-    const auto t3 = clk::now();
-    if (e->iprof && (H.n_pp || H.n_del || H.n_init))
-        fprintf(stderr, "[kwok retire] wait %.3f ms, post %.3f ms\n", ms_between(t1, t2), ms_between(t2, t3));
-    e->host_ms[KWOK_H_WAIT] += ms_between(t1, t2);
-    e->host_ms[KWOK_H_POST] += ms_between(t2, t3);
-    e->host_ms[KWOK_H_TOTAL] += ms_between(t1, t3);
-    e->host_ticks++;
-    e->stats[T.once && !T.once_stream ? KWOK_STAT_TICKS_ONCE : KWOK_STAT_TICKS_FULL]++;
-    if (T.once_stream) e->stats[KWOK_STAT_TICKS_ONCE_STREAM]++;
-    if (T.count_reused) e->stats[KWOK_STAT_TICKS_COUNT_REUSED]++;
-    // a k_once_stream tick that completed cleanly (no error or overflow: returned above; not
-    // redone, not requeued after a device skip): its count is the engine's clean count, and the
-    // slot's handle list is that count's, as is a reused tick's (nothing wrote it)
-    if (T.once_stream && !T.requeued && !T.no_once) {
-        if (!T.count_reused) {
-            e->clean_count.ok = true;
-            e->clean_count.gen = T.state_gen;
-            memcpy(e->clean_count.tot, H.tot, sizeof(H.tot));
-        }
-        kwok_engine::TickSlot::ListValid& L = T.list_valid;
-        L.list = T.hb_nodes, L.n = H.n_hb, L.gen = T.state_gen;
-        L.ok = true;
-    }
-    e->pp_followup = !e->S.cni && H.n_pp != H.n_alloc_local;
-    // the slot's heartbeat region now holds this tick's bodies (TickSlot::HbValid); a
-    // tick that was redone records nothing (hb_record: no heartbeat-once engine, no requeue)
-    if (T.hb_record && !T.no_once) {
-        kwok_engine::TickSlot::HbValid& V = T.hb_valid;
-        V.arena = T.arena, V.n = T.hb_n, V.stride = e->hb_stride, V.units = e->S.hb_units, V.gen = e->hb_gen;
-        V.clock = T.now;
-        V.ok = true;
-    }
-    if (T.hb_prev) e->stats[KWOK_STAT_TICKS_HB_DELTA]++;
-    if (T.once && T.once_use) e->stats[KWOK_STAT_ONCE_SUMMARY]++;  // (a launch that skipped or was redone read none)
-    if (requeue_next) {  // the tick queued behind a redone one skipped on the device
-        if (int rc = enqueue_tick(e, next, true)) {
-            kwok_engine::TickSlot& U = e->slots[next];
-            U.state = SLOT_DONE;
-            U.rc = rc;
-            U.err = e->err;
-            e->poisoned = true;
-        }
-    }
-    return KWOK_OK;
-}
-
-
-// every queued tick finished on the host (before anything that reads or changes
-// the host mirrors or device state outside the tick stream)
-int drain(kwok_engine* e) {
-    for (int i = 0; i < e->nq; i++)
-        if (e->slots[e->queue[i]].state == SLOT_QUEUED) retire(e);  // per-tick failures stay in the slots
-    return KWOK_OK;
-}
-}  // namespace
-
-namespace {
-// what kwok_tick_submit checks before it queues anything
-int tick_submit_check(kwok_engine* e, int64_t now_unix) {
-    if (now_unix < 0 || now_unix > 0xFFFFFFFFll) return e->fail(KWOK_EDOMAIN, "now out of range");
-    if (e->nq >= 2) return e->fail(KWOK_EBUSY, "two ticks outstanding: collect one first");
-    if (e->nq >= 1 && (e->prof || trace_enabled(e)))
-        return e->fail(KWOK_EBUSY, "profiled / traced ticks are not queued behind each other");
-    return KWOK_OK;
-}
-}  // namespace
-
-extern "C" int kwok_tick_submit(kwok_engine* e, int64_t now_unix) {
-    if (!e) return KWOK_EINVAL;
-    if (e->poisoned) return poisoned(e);
-    if (int rc = tick_submit_check(e, now_unix)) return rc;
-    return tick_submit_impl(e, now_unix);
-}
-
-namespace {
-// kwok_tick_submit after its checks (kwok_ingest_pods_packed12_tick queues it
-// behind the batch's apply passes)
-int tick_submit_impl(kwok_engine* e, int64_t now_unix) {
-    const auto t0 = clk::now();
-    // multi rank: the previous tick is finished (its long-list allgather, if any,
-    // included) before this one's collectives are enqueued, so every rank issues
-    // its collectives in the same order whatever its submit / collect pattern
-    if (e->multi) drain(e);
-    if (e->poisoned) return poisoned(e);  // the drained tick failed (its error stays collectable)
-    const auto t_drained = clk::now();
-    int k = -1;
-    for (int pass = 0; pass < 2 && k < 0; pass++)  // prefer keeping the last collected tick's outputs
-        for (int i = 0; i < 2 && k < 0; i++)
-            if (e->slots[i].alloc && e->slots[i].state == SLOT_FREE && (pass == 1 || i != e->cur)) k = i;
-    if (k < 0) {
-        int rc = alloc_slot(e, 1);
-        if (rc) return rc;
-        k = 1;
-    }
-    kwok_engine::TickSlot& T = e->slots[k];
-    int rc = grow_arena(e, T);
-    if (rc) return rc;
-    if (T.rd_pending) {  // the tick's kernels write the arena after the reads queued from it
-        HIPCHK(e, hipStreamWaitEvent(e->st, T.rd, 0));
-        T.rd_pending = false;
-    }
-    if (k == e->cur) e->cur = -1;  // its outputs are overwritten
-    T.now = (uint64_t)now_unix;
-    T.epoch = e->hb_epoch;
-    T.ref_gen[0] = e->refs.gen[0], T.ref_gen[1] = e->refs.gen[1];
-    T.emit_queued = e->emit_hint;
-    e->emit_hint = false;
-    // multi rank: every rank's pods hold the addresses the global pool gave them
-    // unless some rank ever took a foreign one - its flag travels in the exchange
-    // message; a rank that became foreign since the last exchange cannot make a
-    // Use of this tick a change (its Puts come after the Uses, its ingest-time
-    // releases reach the others through kwok_pool_put, which marks them foreign)
-    T.quiet = e->quiet_ok && (e->multi ? !e->foreign_ips && !e->global_foreign : (e->quiet >= 2 || !e->foreign_ips));
-    if (e->quiet < 0xFFFFFFFFu) e->quiet++;
-    rc = enqueue_tick(e, k, false);
-    if (rc) return rc;
-    T.state = SLOT_QUEUED;
-    e->queue[e->nq++] = k;
-    if (e->iprof)
-        fprintf(stderr, "[kwok submit] enqueue %.3f ms (drain %.3f)\n", ms_between(t0, clk::now()), ms_between(t0, t_drained));
-    e->host_ms[KWOK_H_ENQUEUE] += ms_between(t0, clk::now());
-    e->host_ms[KWOK_H_TOTAL] += ms_between(t0, clk::now());
-    return KWOK_OK;
-}
-}  // namespace
-
-extern "C" int kwok_engine_stats(const kwok_engine* e, uint64_t out[KWOK_STAT_COUNT]) {
-    if (!e || !out) return KWOK_EINVAL;
-    for (int i = 0; i < KWOK_STAT_COUNT; i++) out[i] = e->stats[i];
-    return KWOK_OK;
-}
-
-extern "C" int kwok_tick_collect(kwok_engine* e, kwok_tick_result* res) {
-    if (!e) return KWOK_EINVAL;
-    if (e->nq == 0) return e->fail(KWOK_EINVAL, "no tick submitted");
-    const int k = e->queue[0];
-    kwok_engine::TickSlot& T = e->slots[k];
-    if (T.state == SLOT_QUEUED) retire(e);
-    e->queue[0] = e->queue[1];
-    e->queue[1] = -1;
-    e->nq--;
-    T.state = SLOT_FREE;
-    if (T.rc) {
-        e->err = T.err;
-        return T.rc;
-    }
-    e->cur = k;
-    if (res) *res = T.res;
-    return KWOK_OK;
-}
-
-extern "C" int kwok_tick(kwok_engine* e, int64_t now_unix, kwok_tick_result* res) {
-    if (!e) return KWOK_EINVAL;
-    if (e->nq) return e->fail(KWOK_EBUSY, "ticks outstanding: kwok_tick_collect them first");
-    int rc = kwok_tick_submit(e, now_unix);
-    return rc ? rc : kwok_tick_collect(e, res);
 }
 
 int kwok_read_outputs(kwok_engine* e, kwok_outputs* o) {

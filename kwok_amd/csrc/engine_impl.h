@@ -1,5 +1,6 @@
-// engine_impl.h - internal to the host runtime (engine.cpp): owning device / page-locked scratch and the
-// small scoped helpers of its entry points.  Everything here stays out of the dynamic symbol table.
+// engine_impl.h - internal to the host runtime (engine.cpp and engine_tick.cpp, through engine_state.h): owning device /
+// page-locked scratch and the small scoped helpers of its entry points.  Everything here stays out of the dynamic
+// symbol table.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -3,7 +3,7 @@ runs k_once_stream: the heartbeat streamers beside the counting blocks.  The cou
 (handle list, totals) reads state words, never the clock, so a quiet tick that
 follows a cleanly counted one with no state change in between launches the
 streamers alone (k_hb_stream) and takes its header from the engine's clean-count
-record and its handle list from the slot (engine.cpp: kwok_engine::CleanCount,
+record and its handle list from the slot (engine_state.h: kwok_engine::CleanCount,
 TickSlot::ListValid, state_gen).  A reused tick has no net that finds unexpected
 work, so everything here is about WHEN the path is taken.
 

@@ -1,6 +1,6 @@
 """GPU: the delta heartbeat stream.  A tick whose slot provably still holds the
 bodies of the slot's previous tick (same arena, body count, stride, unit count
-and template generation: engine.cpp, TickSlot::HbValid) rewrites only the
+and template generation: engine_state.h, TickSlot::HbValid) rewrites only the
 64-byte lines in which the two templates differ.  The risk is stale bytes, so
 every case here compares EVERY heartbeat body of EVERY tick byte for byte with
 the oracle (gpu_common.compare_tick), compares the whole heartbeat region -

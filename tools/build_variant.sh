@@ -10,6 +10,6 @@ mkdir -p lib/var
   -c ${3:-csrc/kernels.hip} -o lib/var/${4:-kernels}_$1.o
 OBJS="lib/kernels.o lib/ingest.o lib/json.o"
 OBJS=${OBJS/lib\/${4:-kernels}.o/lib\/var\/${4:-kernels}_$1.o}
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o lib/var/libkwok_engine_$1.so lib/engine.o lib/templates.o \
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o lib/var/libkwok_engine_$1.so lib/engine.o lib/engine_tick.o lib/templates.o \
   lib/codec.o lib/gotemplate.o $OBJS -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 strip lib/var/libkwok_engine_$1.so; echo lib/var/libkwok_engine_$1.so
