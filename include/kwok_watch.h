@@ -442,6 +442,57 @@ enum {
 };
 int kwok_refs_stats(kwok_engine* e, uint64_t out[KWOK_REFS_STAT_COUNT]);
 
+/* ---- Node uid directory and batched name lookup -------------------
+ *
+ * A node's uid kept per node slot on the device, and the node directory's
+ * name -> handle lookup for a whole batch, so a caller keeps no per-node map.
+ *
+ * The uid rule, applied behind every node batch while the directory is on, per
+ * bucket in event order (controller.py's _node_put / _node_pop):
+ *   - a DELETE record that ended KWOK_OK marks the slot's uid stale and leaves its
+ *     bytes (a swept node's uid stays answerable under KWOK_REFS_ANY_SLOT);
+ *   - any other record that ended KWOK_OK on a slot with no uid or a stale one
+ *     stores the record's uid and clears stale; on a slot with a live uid it stores
+ *     nothing (a known node keeps its uid);
+ *   - the record's uid: through kwok_ingest_nodes_framed / _framed_echo the frame's
+ *     uid span in the resident stream, if the frame has no KWOK_FRAME_ESC_UID and the
+ *     uid is 1..KWOK_UID_MAX bytes; otherwise, and through every other entry
+ *     (kwok_ingest_nodes, kwok_ingest_nodes_json, a sweep's DELETE records), none:
+ *     length 0 is stored, so a reused slot never answers its previous node's uid.
+ *     Nothing is truncated or guessed.
+ * With the directory on, the reference directory's node answers carry the uid behind
+ * the name: a node whose uid is not stale answers it, else uid_len 0;
+ * KWOK_REFS_ANY_SLOT (and kwok_read_refs) answers what the slot last stored, stale
+ * or not, and a slot whose entry is gone but whose uid remains answers KWOK_REF_NONE
+ * with that uid.  With it off every node answer is what it was.
+ * Single-rank engines only (kwok_node_lookup excepted). */
+/* Allocates the directory (idempotent): KWOK_UID_MAX + 9 bytes per node slot (the uid, its length byte and
+ * the key of the entry it was stored for: a placeholder made in a freed slot never answers another node's uid).  Nodes that
+ * exist have no uid until bound.  KWOK_EINVAL on a multi-rank engine. */
+int kwok_node_dir_enable(kwok_engine* e);
+/* out_handles[i]: the existing node named arena[off[i], +len[i]), or -1 (an empty name, one
+ * over KWOK_REF_NAME_MAX bytes, one in a bucket this rank does not own, a deleted node that
+ * pods still reference, a placeholder).  kwok_node_has for a batch, answering handles.
+ * Needs no directory enabled; drains submitted ticks first. */
+int kwok_node_lookup(kwok_engine* e, const char* arena, const uint64_t* off, const uint32_t* len, size_t n,
+                     int32_t* out_handles);
+/* uid i = arena[off[i], +len[i]) becomes the uid of existing node handles[i] (replacing a
+ * stored one, clearing stale).  Counted in *n_bad, storing nothing: a handle out of range or
+ * of no existing node, a uid that is empty or longer than KWOK_UID_MAX. */
+int kwok_node_bind(kwok_engine* e, const int32_t* handles, const char* arena, const uint64_t* off,
+                       const uint32_t* len, size_t n, size_t* n_bad);
+enum {
+    KWOK_NODE_DIR_STAT_LOOKUPS = 0, /* names probed (kwok_node_lookup and the echo entry's dropped records) */
+    KWOK_NODE_DIR_STAT_HITS,        /* ... that resolved to an existing node */
+    KWOK_NODE_DIR_STAT_NOTES,       /* uids stored by ingests */
+    KWOK_NODE_DIR_STAT_BINDS,       /* uids stored by kwok_node_bind */
+    KWOK_NODE_DIR_STAT_UNBOUND,     /* creates stored without a uid (an entry or a frame that carries none) */
+    KWOK_NODE_DIR_STAT_BYTES,       /* device memory the directory holds */
+    KWOK_NODE_DIR_STAT_COUNT
+};
+/* All zero while the directory is off. */
+int kwok_node_dir_stats(kwok_engine* e, uint64_t out[KWOK_NODE_DIR_STAT_COUNT]);
+
 #ifdef __cplusplus
 }
 #endif

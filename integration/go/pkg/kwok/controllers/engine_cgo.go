@@ -754,6 +754,59 @@ func (g *gpuEngine) readRefs(which, first, count int) ([]objRef, error) {
 	return out, nil
 }
 
+// ---- the node uid directory (kwok_watch.h, DESIGN.md §26) ----
+
+// nodeDirEnable: kwok_node_dir_enable (idempotent; single-rank engines only): a uid per node slot on the
+// device; the node answers of refsLookup / readRefs then carry the uid behind the name
+func (g *gpuEngine) nodeDirEnable() error {
+	if rc := C.kwok_node_dir_enable(g.h); rc != C.KWOK_OK {
+		return fmt.Errorf("kwok_node_dir_enable: %d: %s", int(rc), g.lastError())
+	}
+	return nil
+}
+
+// nodeSpans: strings -> (arena, offsets, lengths), as uidSpans
+func nodeSpans(ss []string) ([]byte, []uint64, []uint32) {
+	var arena []byte
+	offs, lens := make([]uint64, len(ss)), make([]uint32, len(ss))
+	for i, s := range ss {
+		offs[i], lens[i] = uint64(len(arena)), uint32(len(s))
+		arena = append(arena, s...)
+	}
+	return append(arena, 0), offs, lens
+}
+
+// nodeLookup: kwok_node_lookup - the handle of the existing node of each name, or -1
+func (g *gpuEngine) nodeLookup(names []string) ([]int32, error) {
+	out := make([]int32, len(names))
+	if len(names) == 0 {
+		return out, nil
+	}
+	arena, offs, lens := nodeSpans(names)
+	rc := C.kwok_node_lookup(g.h, (*C.char)(unsafe.Pointer(&arena[0])), (*C.uint64_t)(&offs[0]), (*C.uint32_t)(&lens[0]),
+		C.size_t(len(names)), (*C.int32_t)(&out[0]))
+	if rc < 0 {
+		return nil, fmt.Errorf("kwok_node_lookup: %d: %s", int(rc), g.lastError())
+	}
+	return out, nil
+}
+
+// nodeBind: kwok_node_bind - uids[i] becomes the uid of existing node handles[i]; returns the records that
+// stored nothing
+func (g *gpuEngine) nodeBind(handles []int32, uids []string) (int, error) {
+	if len(handles) == 0 {
+		return 0, nil
+	}
+	arena, offs, lens := nodeSpans(uids)
+	var bad C.size_t
+	rc := C.kwok_node_bind(g.h, (*C.int32_t)(&handles[0]), (*C.char)(unsafe.Pointer(&arena[0])), (*C.uint64_t)(&offs[0]),
+		(*C.uint32_t)(&lens[0]), C.size_t(len(handles)), &bad)
+	if rc < 0 {
+		return 0, fmt.Errorf("kwok_node_bind: %d: %s", int(rc), g.lastError())
+	}
+	return int(bad), nil
+}
+
 // ---- the echo ledger (kwok_watch.h, DESIGN.md §24) ----
 const (
 	echoNote   = uint8(C.KWOK_ECHO_NOTE)

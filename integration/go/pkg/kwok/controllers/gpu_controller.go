@@ -253,6 +253,12 @@ type GPUController struct {
 	// kwok_refs_lookup, the typed paths name their pods with kwok_refs_bind (bindBatch)
 	refDir      bool
 	batchRefs   map[types.UID]types.NamespacedName // refDir: the typed batch's names by uid (bindBatch)
+	// nodeDir (KWOK_NODE_DIR=1, with the three switches above): the engine's node uid directory (kwok_watch.h,
+	// DESIGN.md §26) holds a uid per node slot and resolves names to handles in batches (kwok_node_lookup);
+	// nodeHandle stays empty too: typed pod events resolve spec.nodeName per run, typed node events bind
+	// their uids with kwok_node_bind (this source has no relist sweep; controller.py's takes the swept
+	// nodes' uids from kwok_refs_lookup)
+	nodeDir     bool
 	gpuCodec    bool // pod documents decoded on the GPU (kwok_ingest_pods_json); KWOK_GPU_CODEC=0: the host codec
 	podDocsHost int  // pod documents the GPU codec left to the host codec (logged)
 	nodeDocsHost int // node documents the GPU codec left to the host codec (logged)
@@ -307,8 +313,21 @@ func newGPUController(conf Config, interval time.Duration) (*GPUController, erro
 			return nil, err
 		}
 	}
+	nodeDir := os.Getenv("KWOK_NODE_DIR") == "1"
+	if nodeDir {
+		if !refDir {
+			codec.close()
+			eng.close()
+			return nil, fmt.Errorf("KWOK_NODE_DIR=1 needs KWOK_UID_DIR=1, KWOK_ECHO_LEDGER=1 and KWOK_REF_DIR=1")
+		}
+		if err := eng.nodeDirEnable(); err != nil {
+			codec.close()
+			eng.close()
+			return nil, err
+		}
+	}
 	return &GPUController{
-		byUID: byUID, refDir: refDir, batchRefs: map[types.UID]types.NamespacedName{},
+		byUID: byUID, refDir: refDir, nodeDir: nodeDir, batchRefs: map[types.UID]types.NamespacedName{},
 		conf: conf, eng: eng, codec: codec, interval: interval, finalizer: finalizerPatch(),
 		nodeName: map[int32]string{}, nodeHandle: map[string]int32{}, podByUID: map[types.UID]int32{},
 		podUID: map[int32]types.UID{},
@@ -812,6 +831,7 @@ func (c *GPUController) flushNodes(ctx context.Context, b objBatch) error {
 		return err
 	}
 	c.nodeDocsHost += nHost
+	bound := map[int32]string{} // nodeDir: handle -> the uid of its last upsert (a typed event carries none to the device)
 	for i := range ops {
 		if ss[i] != C.KWOK_OK {
 			if ss[i] == C.KWOK_EDOMAIN || ss[i] == C.KWOK_EINVAL { // outside the engine's domain (DESIGN.md §2)
@@ -823,8 +843,21 @@ func (c *GPUController) flushNodes(ctx context.Context, b objBatch) error {
 		if b.del[i] {
 			delete(c.nodeName, hs[i])
 			delete(c.nodeHandle, name)
+			delete(bound, hs[i])
 		} else {
 			c.putNode(hs[i], name)
+			bound[hs[i]] = string(b.uids[i])
+		}
+	}
+	if c.nodeDir {
+		bh, bu := make([]int32, 0, len(bound)), make([]string, 0, len(bound))
+		for h, u := range bound {
+			if len(u) > 0 && len(u) <= C.KWOK_UID_MAX {
+				bh, bu = append(bh, h), append(bu, u)
+			}
+		}
+		if _, err := c.eng.nodeBind(bh, bu); err != nil {
+			return err
 		}
 	}
 	return nil
@@ -833,6 +866,9 @@ func (c *GPUController) flushNodes(ctx context.Context, b objBatch) error {
 // putNode: a node the engine created or updated - its handle by name and, without the reference directory,
 // its name by handle
 func (c *GPUController) putNode(h int32, name string) {
+	if c.nodeDir { // (the device holds the name, the handle and the uid)
+		return
+	}
 	if !c.refDir {
 		c.nodeName[h] = name
 	}
@@ -1067,6 +1103,30 @@ func (c *GPUController) flushPodsHost(ctx context.Context, tasks *parallelTasks,
 	flush := func() error {
 		evs := make([]C.kwok_pod_event, 0, len(run))
 		keep := run[:0]
+		on := c.nodeHandle // name -> handle of the nodes the engine holds
+		if c.nodeDir {     // ... resolved for the run's names by one kwok_node_lookup
+			on = map[string]int32{}
+			var names []string
+			for _, r := range run {
+				if nm := str(b.arena, docs[r.i].ev.node_name); !b.del[r.i] {
+					if _, seen := on[nm]; !seen {
+						on[nm] = -1
+						names = append(names, nm)
+					}
+				}
+			}
+			nhs, err := c.eng.nodeLookup(names)
+			if err != nil {
+				return err
+			}
+			for k, nm := range names {
+				if nhs[k] >= 0 {
+					on[nm] = nhs[k]
+				} else {
+					delete(on, nm)
+				}
+			}
+		}
 		for _, r := range run {
 			d := &docs[r.i]
 			h, known := c.podByUID[b.uids[r.i]]
@@ -1101,7 +1161,7 @@ func (c *GPUController) flushPodsHost(ctx context.Context, tasks *parallelTasks,
 				// the node by handle when the engine holds it (no name lookup on the host);
 				// otherwise by spec.nodeName (a deleted node pods still reference, or none yet)
 				d.ev.node_handle = -1
-				if nh, ok := c.nodeHandle[str(b.arena, d.ev.node_name)]; ok {
+				if nh, ok := on[str(b.arena, d.ev.node_name)]; ok {
 					d.ev.node_handle = C.int32_t(nh)
 				}
 			}

@@ -137,6 +137,7 @@ REF_NONE = 3        # KWOK_REF_NONE: kwok_ref.status of a live pod with no name 
 REFS_ANY_SLOT = 1   # KWOK_REFS_ANY_SLOT: kwok_refs_lookup answers what the slot last stored, live or not
 REFS_HEARTBEAT, REFS_NODE_INIT, REFS_POD_PATCH, REFS_DELETE = range(4)  # KWOK_REFS_*: the tick's output lists
 REFS_STATS = ("binds", "notes", "unnamed", "reads", "not_found", "bytes")  # KWOK_REFS_STAT_* order
+NODE_DIR_STATS = ("lookups", "hits", "notes", "binds", "unbound", "bytes")  # KWOK_NODE_DIR_STAT_* order
 
 
 class Ref(C.Structure):

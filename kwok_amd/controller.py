@@ -311,7 +311,7 @@ class Controller:
                     max_pod_specs=4096)
 
     def __init__(self, conf: Config, backend=None, codec_threads=1, suppress_echoes=True, geometry=None,
-                 gpu_codec=True, uid_directory=False, echo_ledger=False, ref_directory=False):
+                 gpu_codec=True, uid_directory=False, echo_ledger=False, ref_directory=False, node_directory=False):
         self.conf = conf
         # uid_directory: the engine's pod uid directory (kwok_watch.h) resolves metadata.uid -> handle on
         # the device; pod_by_uid stays empty (a uid the directory cannot key - empty, escaped in the
@@ -356,6 +356,15 @@ class Controller:
             if not hasattr(self.eng, "refs_enable"):
                 raise ValueError("ref_directory needs the engine backend (kwok_refs_enable)")
             self.eng.refs_enable()
+        # node_directory: the engine's node uid directory (kwok_watch.h) holds a uid per node slot and resolves
+        # names to handles in batches: node_handle and node_uid stay empty too
+        self.node_dir = bool(node_directory)
+        if self.node_dir:
+            if not (uid_directory and echo_ledger and ref_directory):
+                raise ValueError("node_directory needs uid_directory=True, echo_ledger=True and ref_directory=True")
+            if not hasattr(self.eng, "node_dir_enable"):
+                raise ValueError("node_directory needs the engine backend (kwok_node_dir_enable)")
+            self.eng.node_dir_enable()
         self.hb_refs = []     # ref_directory: the heartbeat list's references of epoch hb_epoch
         self.codec = Codec(manage_all_nodes=conf.manage_all_nodes,
                            manage_nodes_with_annotation_selector=conf.manage_nodes_with_annotation_selector,
@@ -572,6 +581,7 @@ class Controller:
         hs, st, nh = self.eng.ingest_nodes_json(self.codec, arena, offs, lens, ops)
         self.stats.node_docs_host += nh
         self.stats.node_records += int(np.isin(st, (abi.EDOMAIN, abi.EINVAL), invert=True).sum())
+        bound = {}  # node_directory: handle -> the uid of its last upsert (a typed event carries none to the device)
         for k, w in enumerate(ws):
             name = _meta(w.obj).get("name", "")
             if st[k] != abi.OK:
@@ -580,11 +590,32 @@ class Controller:
                 continue
             if w.deleted:
                 self._node_pop(int(hs[k]), name)
+                bound.pop(int(hs[k]), None)
             else:
                 self._node_put(int(hs[k]), name, w.uid)
+                bound[int(hs[k])] = w.uid
+        self._node_bind(bound)
+
+    def _node_bind(self, bound):
+        """node_directory: the nodes a typed batch created or updated are bound to their uids on the device
+        (where the pod paths call kwok_uid_bind), so that a sweep finds the uid whose notes it forgets"""
+        if not self.node_dir:
+            return
+        ok = [(h, u) for h, u in bound.items() if u and 0 < len(u.encode()) <= abi.UID_MAX]
+        if ok:
+            self.eng.node_bind([h for h, _u in ok], [u for _h, u in ok])
+
+    def _node_handles(self, names):
+        """node_directory: name -> handle of the existing nodes among names, by one kwok_node_lookup"""
+        names = list(dict.fromkeys(names))
+        hs = self.eng.node_lookup(names) if names else []
+        return {n: int(h) for n, h in zip(names, hs) if h >= 0}
 
     def _node_put(self, h, name, uid=None):
-        """a node the engine created or updated: its handle by name (and, ref_directory off, its name by handle)"""
+        """a node the engine created or updated: its handle by name (and, ref_directory off, its name by handle);
+        node_directory: the device holds all three"""
+        if self.node_dir:
+            return
         if not self.refs:
             self.node_name[h] = name
         self.node_handle[name] = h
@@ -592,6 +623,8 @@ class Controller:
             self.node_uid[h] = uid
 
     def _node_pop(self, h, name):
+        if self.node_dir:
+            return
         self.node_name.pop(h, None)
         self.node_handle.pop(name, None)
         self.node_uid.pop(h, None)
@@ -645,6 +678,10 @@ class Controller:
             return self._flush_pods_gpu(ws, docs)
         b = self.codec.decode_pods(docs, strict=False, threads=self.threads)
         idx, recs = [], []
+        # the node by handle when the engine holds it; otherwise by spec.nodeName (node_directory: the batch's
+        # names resolved by one kwok_node_lookup)
+        on = self.node_handle if not self.node_dir else self._node_handles(
+            b.text(b.pods[i].ev.node_name) for i, w in enumerate(ws) if b.status[i] == abi.OK and not w.deleted)
         for i, w in enumerate(ws):
             if b.status[i] != abi.OK:
                 self.stats.rejected.append(("pod", _meta(w.obj).get("name"), b.status[i]))
@@ -662,8 +699,7 @@ class Controller:
                 except Exception as ex:  # KWOK_EDOMAIN: outside the supported domain
                     self.stats.rejected.append(("pod-spec", b.text(d.name), str(ex)))
                     continue
-                # the node by handle when the engine holds it; otherwise by spec.nodeName
-                r["node_handle"] = self.node_handle.get(b.text(d.ev.node_name), -1)
+                r["node_handle"] = on.get(b.text(d.ev.node_name), -1)
             idx.append(i)
             recs.append(r)
         if not recs:
@@ -772,6 +808,14 @@ class Controller:
             self.stats.resync_skipped += 1
             return
         hs, _rel, nd = self.eng.resync_sweep(kind)
+        if nodes and self.node_dir:
+            # the swept nodes' slots keep their uids (stale) until the next node ingest: no map is inverted
+            for _st, _ns, _name, uid in (self.eng.ref_items(*self.eng.refs_lookup(abi.KIND_NODES, hs, abi.REFS_ANY_SLOT))
+                                         if len(hs) else []):
+                self._forget(uid.decode())
+            self.stats.resync_swept_nodes += len(hs)
+            self._send_echo()
+            return
         if nodes:
             # (ref_directory: a swept node's entry may be gone with its name; node_handle still names it)
             by_handle = {v: k for k, v in self.node_handle.items()} if self.refs and len(hs) else self.node_name
@@ -937,13 +981,19 @@ class Controller:
                                        ty[esc] == abi.WATCH_DELETED)
             self.stats.echoes_at_flush += int(drop.sum())
             st[esc[drop != 0]] = abi.ECHO
-            if nodes:  # (an echo's handle: the name the controller knows)
+            if nodes and self.node_dir:  # (an echo's handle: the decoded name, resolved by the device)
+                dropped = esc[drop != 0]
+                if len(dropped):
+                    hs[dropped] = self.eng.node_lookup([name(i) for i in dropped])
+            elif nodes:  # (an echo's handle: the name the controller knows)
                 for i in esc[drop != 0]:
                     hs[i] = self.node_handle.get(name(i), -1)
             late = esc[drop == 0].astype(np.uint32)
             if len(late):
                 if nodes:
                     hs[late], st[late], nh2 = self.eng.ingest_nodes_framed(self.codec, sid, late)
+                    if self.node_dir:
+                        self._bind_escaped_uids(late, hs, st, ty, uid_of)
                 else:
                     hs[late], st[late], _rel, nh2, r2 = self.eng.ingest_pods_framed_uid(self.codec, sid, late)
                     runs += r2
@@ -956,6 +1006,8 @@ class Controller:
         if nodes:
             self.stats.node_docs_host += nh
             self.stats.node_records += int(np.isin(st[keep], (abi.EDOMAIN, abi.EINVAL), invert=True).sum())
+            if self.node_dir:  # the device keeps name, handle and uid of every record: only the rejected ones are looked at
+                keep = keep[st[keep] != abi.OK]
             for i in keep.tolist():
                 h = int(hs[i])
                 if st[i] != abi.OK:
@@ -1009,6 +1061,19 @@ class Controller:
             elif h not in self.pod_ref:  # a create (a known pod keeps its uid and name)
                 self.pod_uid[h] = uid_of(i)
                 self.pod_ref[h] = (ns(i), name(i))
+
+    def _bind_escaped_uids(self, late, hs, st, ty, uid_of):
+        """node_directory: a kept node frame whose uid holds an escape stored no uid on the device (the span is
+        the raw text); a node that has none afterwards - a create, as `h not in node_uid` decides it on the host -
+        is bound to the decoded text"""
+        first = {}  # handle -> its first such frame (the rule keeps a known node's uid)
+        for i in late.tolist():
+            if st[i] == abi.OK and ty[i] != abi.WATCH_DELETED:
+                first.setdefault(int(hs[i]), i)
+        if not first:
+            return
+        refs, _blob = self.eng.refs_lookup(abi.KIND_NODES, list(first))
+        self._node_bind({h: uid_of(i) for (h, i), ul in zip(first.items(), refs["uid_len"].tolist()) if ul == 0})
 
     def _setup_cni(self):
         hs = self.eng.cni_pending()

@@ -14,6 +14,7 @@
 // The tick queue (output slots and arena, enqueue / retire, submit / collect) is engine_tick.cpp;
 // engine_state.h holds the state both files work on.
 #include "engine_state.h"
+#include "node_spans.h"
 
 
 namespace {
@@ -1240,6 +1241,11 @@ int ingest_nodes_impl(kwok_engine* e, const kwok_node_event* ev, size_t n, const
         N.force = 1;
         if ((rc = sort_apply_results())) return failed(rc);
     }
+    if (e->ndir.on) {  // the uid rule behind the batch's last apply pass (reads its results; no node_state is written)
+        const NodeUidNote none{};
+        launch_nd_uid_note(e->S, N, e->ndir.dir(), e->ndir.note ? *e->ndir.note : none, st);
+        if (hipGetLastError() != hipSuccess) return failed(e->fail(KWOK_EDEVICE, "node uid note"));
+    }
     if (e->resync.open[KWOK_KIND_NODES]) {  // the batch's final results mark their nodes (before the buffers' next use)
         launch_seen_mark_nodes(e->S, N, e->resync.node_seen, e->resync.ctr, st);
         HIPCHK(e, hipGetLastError());
@@ -2020,6 +2026,56 @@ int json_nodes_listed(kwok_engine* e, uint32_t nh, std::vector<uint32_t>& list) 
     std::sort(list.begin(), list.end());
     return KWOK_OK;
 }
+// The documents the device listed for the host (list: their batch indices, sorted): the host codec on a
+// private copy of each (it writes the canonical blobs over their spans); their records to the device,
+// spans moved to the batch's arena (the device only bounds-checks the blob spans: the host completion
+// interns the canonical bytes from the private copy).  doc(i): document i's span in arena and its op.
+// hstat[q]: the host decode's status of list[q]; hdoc / hrec / hbuf: what NodeJsonCtx carries on.
+int nodes_complete_listed(kwok_engine* e, const kwok_codec* c, const char* arena, const std::vector<uint32_t>& list,
+                          const std::function<void(uint32_t, uint64_t*, uint32_t*, uint8_t*)>& doc, std::vector<int32_t>& hstat,
+                          std::unordered_map<uint32_t, uint32_t>& hdoc, std::vector<kwok_node_event>& hrec,
+                          std::vector<std::string>& hbuf) {
+    auto& G = e->ing;
+    auto& J = e->json;
+    hipStream_t st = e->st;
+    const uint32_t nh = (uint32_t)list.size();
+    std::vector<kwok_node_event> hdev(nh);
+    hrec.assign(nh, kwok_node_event{});
+    hbuf.assign(nh, std::string());
+    hstat.assign(nh, KWOK_OK);
+    const bool par = nh >= NODE_PAR_MIN && e->n_part > 1;
+    run_parts(e, par, [&](int p) {
+        const size_t lo = par ? (size_t)nh * p / e->n_part : (p ? nh : 0);
+        const size_t hi = par ? (size_t)nh * (p + 1) / e->n_part : nh;
+        for (size_t q = lo; q < hi; q++) {
+            uint64_t off = 0;
+            uint32_t len = 0;
+            uint8_t op = KWOK_OP_UPSERT;
+            doc(list[q], &off, &len, &op);
+            hbuf[q].assign(arena + off, len);
+            kwok_node_event x{};
+            const int r = kwok_decode_node(c, hbuf[q].data(), hbuf[q].size(), 0, hbuf[q].size(), &x);
+            hrec[q] = x;
+            kwok_node_event d = x;
+            auto mv = [&](kwok_str& s) {
+                if (s.len) s.off += (uint32_t)off;
+            };
+            mv(d.name), mv(d.addresses), mv(d.allocatable), mv(d.capacity);
+            for (int k = 0; k < KWOK_NI_COUNT; k++) mv(d.node_info[k]);
+            d.op = r == KWOK_OK ? op : (uint8_t)0xFF;
+            if (r != KWOK_OK) d.name = kwok_str{0, 0};
+            hdev[q] = d;
+            hstat[q] = r;
+        }
+    });
+    for (uint32_t q = 0; q < nh; q++) hdoc.emplace(list[q], q);
+    HIPCHK(e, hipMemcpyAsync(J.host_list, list.data(), (size_t)nh * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(J.nev_fix, hdev.data(), (size_t)nh * sizeof(kwok_node_event), hipMemcpyHostToDevice, st));
+    launch_node_scatter(G.d_nev, J.nev_fix, J.host_list, nh, st);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipStreamSynchronize(st));  // (hdev is read by the copy above)
+    return KWOK_OK;
+}
 }  // namespace
 
 // kwok_ingest_nodes_json: WatchNodes / ListNodes from the documents themselves
@@ -2060,46 +2116,19 @@ int ingest_nodes_json_impl(kwok_engine* e, const kwok_codec* c, const char* aren
     uint32_t nh = 0;
     int rc = json_nodes_decode(e, c, arena, arena_len, doc_off, doc_len, op, n, dstat, &nh, resident);
     if (rc) return rc;
-    auto& G = e->ing;
-    auto& J = e->json;
-    hipStream_t st = e->st;
-    // the listed documents: the host codec on a private copy of each (it writes the
-    // canonical blobs over their spans); their records to the device, spans moved to
-    // the batch's arena (the device only bounds-checks the blob spans: the host
-    // completion below interns the canonical bytes from the private copy)
+    // the listed documents, completed by the host codec
     std::unordered_map<uint32_t, uint32_t> hdoc;
-    std::vector<kwok_node_event> hrec(nh), hdev(nh);
-    std::vector<std::string> hbuf(nh);
+    std::vector<kwok_node_event> hrec;
+    std::vector<std::string> hbuf;
     if (nh) {
         std::vector<uint32_t> list;
+        std::vector<int32_t> hstat;
         if ((rc = json_nodes_listed(e, nh, list))) return rc;
-        const bool par = nh >= NODE_PAR_MIN && e->n_part > 1;
-        run_parts(e, par, [&](int p) {
-            const size_t lo = par ? (size_t)nh * p / e->n_part : (p ? nh : 0);
-            const size_t hi = par ? (size_t)nh * (p + 1) / e->n_part : nh;
-            for (size_t q = lo; q < hi; q++) {
-                const uint32_t i = list[q];
-                hbuf[q].assign(arena + doc_off[i], doc_len[i]);
-                kwok_node_event x{};
-                const int r = kwok_decode_node(c, hbuf[q].data(), hbuf[q].size(), 0, hbuf[q].size(), &x);
-                hrec[q] = x;
-                kwok_node_event d = x;
-                auto mv = [&](kwok_str& s) {
-                    if (s.len) s.off += (uint32_t)doc_off[i];
-                };
-                mv(d.name), mv(d.addresses), mv(d.allocatable), mv(d.capacity);
-                for (int k = 0; k < KWOK_NI_COUNT; k++) mv(d.node_info[k]);
-                d.op = r == KWOK_OK ? op[i] : (uint8_t)0xFF;
-                if (r != KWOK_OK) d.name = kwok_str{0, 0};
-                hdev[q] = d;
-                dstat[i] = r;
-            }
-        });
-        for (uint32_t q = 0; q < nh; q++) hdoc.emplace(list[q], q);
-        HIPCHK(e, hipMemcpyAsync(J.host_list, list.data(), (size_t)nh * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(e, hipMemcpyAsync(J.nev_fix, hdev.data(), (size_t)nh * sizeof(kwok_node_event), hipMemcpyHostToDevice, st));
-        launch_node_scatter(G.d_nev, J.nev_fix, J.host_list, nh, st);
-        HIPCHK(e, hipGetLastError());
+        if ((rc = nodes_complete_listed(e, c, arena, list, [&](uint32_t i, uint64_t* o, uint32_t* l, uint8_t* p) {
+                *o = doc_off[i], *l = doc_len[i], *p = op[i];
+            }, hstat, hdoc, hrec, hbuf)))
+            return rc;
+        for (uint32_t q = 0; q < nh; q++) dstat[list[q]] = hstat[q];
     }
     if (n_host) *n_host = nh;
     if (e->iprof)
@@ -2386,6 +2415,19 @@ int kwok_ingest_nodes_framed(kwok_engine* e, const kwok_codec* c, uint64_t strea
     int rc = framed_records(e, stream_id, frame_idx, n, off, len, op);
     if (rc) return rc;
     Wt.stats[KWOK_WATCH_STAT_INGESTS]++;
+    // the node uid directory: the records' uid spans in the resident stream, for the note behind the apply pass
+    auto& D = e->ndir;
+    NodeUidNote un{};
+    if (D.on && n) {  // (read from the resident frames by the uploaded indices: k_nd_frame_recs, not strict)
+        if (e->poisoned) return poisoned(e);
+        if ((rc = D.recs.reserve(e, n))) return rc;
+        HIPCHK(e, hipMemcpyAsync(D.fidx, frame_idx, n * 4, hipMemcpyHostToDevice, e->st));
+        launch_nd_frame_recs(Wt.frames, (uint32_t)Wt.frames_h.size(), Wt.len, D.fidx, (uint32_t)n, false, nullptr, nullptr, nullptr,
+                             D.uoff, D.ulen, nullptr, e->st);
+        HIPCHK(e, hipGetLastError());
+        un = NodeUidNote{Wt.stream, Wt.len, D.uoff, D.ulen};
+    }
+    ScopedPtr<NodeUidNote> uids(D.note, D.on && n ? &un : nullptr);
     ScopedPtr<uint8_t> src(e->ing.arena_src, Wt.stream);  // the ingest kernels read the batch's strings from the resident stream
     return ingest_nodes_json_impl(e, c, Wt.host, Wt.len, off.data(), len.data(), op.data(), n, out_handles, out_status,
                                   n_host, Wt.stream);
@@ -3334,6 +3376,90 @@ int kwok_ingest_pods_framed_echo(kwok_engine* e, const kwok_codec* c, uint64_t s
     return rejected;
 }
 
+namespace {
+// The device-input form of kwok_ingest_nodes_framed (the node directory on): record k is frame didx[k] of the
+// resident stream, didx a device-resident list that names ingestible frames only (the echo filter's kept records).
+// k_nd_frame_recs writes the decode's inputs and the uid spans, k_json_nodes runs over the resident stream in one
+// piece, the documents it lists for the host are completed as kwok_ingest_nodes_json completes them (their indices
+// and the list fetched only when there are any; their spans from Wt.frames_h), ingest_nodes_impl applies the
+// records where they are, the note follows.  Nothing per record comes back: the apply's handles and statuses stay
+// in ing.out_handle / out_status, the decode's in json.nstat, for k_nd_echo_fix.  The caller drained and checked
+// the stream.  Returns the apply's rejected count (not the call's), or an error.
+int nodes_framed_dev_impl(kwok_engine* e, const kwok_codec* c, const uint32_t* didx, size_t n, size_t* n_host) {
+    auto& Wt = e->watch;
+    auto& G = e->ing;
+    auto& J = e->json;
+    auto& D = e->ndir;
+    hipStream_t st = e->st;
+    e->emit_hint = true;
+    e->quiet = 0;
+    e->state_changed();
+    Wt.stats[KWOK_WATCH_STAT_INGESTS]++;
+    int rc = 0;
+    if ((rc = node_reserve(e, n, 0)) || (rc = json_reserve(e, n)) || (rc = J.node_docs.reserve(e, n)) || (rc = D.recs.reserve(e, n)))
+        return rc;
+    if ((rc = codec_export(c, J.cfg_h))) {  // (selectors beyond the device tables: every document to the host)
+        if (rc != KWOK_EDOMAIN) return e->fail(rc, "%s", kwok_codec_last_error());
+        memset(J.cfg_h, 0, sizeof(JsonCfg));
+        J.cfg_h->all_host = 1;
+    }
+    HIPCHK(e, hipMemcpyAsync(J.cfg, J.cfg_h, sizeof(JsonCfg), hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemsetAsync(J.n_host, 0, 4, st));
+    HIPCHK(e, hipMemsetAsync(&D.call->err, 0, sizeof(D.call->err), st));
+    launch_nd_frame_recs(Wt.frames, (uint32_t)Wt.frames_h.size(), Wt.len, didx, (uint32_t)n, true, J.off, J.len, J.op, D.uoff, D.ulen,
+                         &D.call->err, st);
+    HIPCHK(e, hipGetLastError());
+    JsonNodeArgs A{};
+    A.arena = Wt.stream;
+    A.arena_len = Wt.len;
+    A.doc_off = J.off, A.doc_len = J.len, A.op = J.op;
+    A.n = (uint32_t)n;
+    A.cfg = J.cfg;
+    A.ev = G.d_nev;
+    A.status = J.nstat;
+    A.host_list = J.host_list;
+    A.n_host = J.n_host;
+    A.base = 0;
+    launch_json_nodes(A, st);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(J.n_host_h, J.n_host, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipMemcpyAsync(D.call_h, D.call, sizeof(*D.call_h.p), hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    if (D.call_h->err) {  // (an engine bug: the echo filter kept an index that names no ingestible frame)
+        e->poisoned = true;
+        return e->fail(KWOK_EDEVICE, "device-input node ingest: a kept index names no ingestible frame");
+    }
+    const uint32_t nh = *J.n_host_h;
+    if (nh > n) return e->fail(KWOK_EDEVICE, "device-input node ingest: %u of %zu documents listed", nh, n);
+    std::unordered_map<uint32_t, uint32_t> hdoc;
+    std::vector<kwok_node_event> hrec;
+    std::vector<std::string> hbuf;
+    if (nh) {
+        std::vector<uint32_t> list, kidx(n);
+        std::vector<int32_t> hstat;
+        HIPCHK(e, hipMemcpyAsync(kidx.data(), didx, n * 4, hipMemcpyDeviceToHost, st));
+        if ((rc = json_nodes_listed(e, nh, list))) return rc;  // (synchronises: kidx is here too)
+        if (!listed_in_range(list, kidx, Wt.frames_h.size())) return e->fail(KWOK_EDEVICE, "device-input node ingest: a listed document out of range");
+        if ((rc = nodes_complete_listed(e, c, Wt.host, list, [&](uint32_t i, uint64_t* o, uint32_t* l, uint8_t* p) {
+                const kwok_watch_frame& f = Wt.frames_h[kidx[i]];
+                *o = f.doc_off, *l = f.doc_len, *p = f.type == KWOK_WATCH_DELETED ? KWOK_OP_DELETE : KWOK_OP_UPSERT;
+            }, hstat, hdoc, hrec, hbuf)))
+            return rc;
+        // the host codec's statuses of those documents, beside the device's in json.nstat
+        HIPCHK(e, hipMemcpyAsync(D.hstat, hstat.data(), (size_t)nh * 4, hipMemcpyHostToDevice, st));
+        launch_nd_stat_scatter(J.nstat, J.host_list, D.hstat, nh, st);
+        HIPCHK(e, hipGetLastError());
+        HIPCHK(e, hipStreamSynchronize(st));  // (hstat is read by the copy above)
+    }
+    if (n_host) *n_host = nh;
+    const NodeUidNote un{Wt.stream, Wt.len, D.uoff, D.ulen};
+    ScopedPtr<NodeUidNote> uids(D.note, &un);
+    ScopedPtr<uint8_t> src(G.arena_src, Wt.stream);  // the ingest kernels read the batch's strings from the resident stream
+    NodeJsonCtx ctx{Wt.host, &hdoc, &hrec, &hbuf};
+    return ingest_nodes_impl(e, nullptr, n, Wt.host, Wt.len, nullptr, nullptr, &ctx);
+}
+}  // namespace
+
 int kwok_ingest_nodes_framed_echo(kwok_engine* e, const kwok_codec* c, uint64_t stream_id, const uint32_t* frame_idx,
                                   size_t n, int32_t* out_handles, int32_t* out_status, size_t* n_host,
                                   size_t* n_echoes) {
@@ -3351,6 +3477,35 @@ int kwok_ingest_nodes_framed_echo(kwok_engine* e, const kwok_codec* c, uint64_t 
     EchoKeep K{};
     if ((rc = echo_filter_frames(e, frame_idx, n, &B, &F, &K))) return rc;
     const size_t nk = E.call_h->n_keep, nd = E.call_h->n_drop;
+    if (e->ndir.on) {
+        // the node directory on: the kept records are ingested from the resident frames by the device-resident
+        // index list, every answer is merged on the device, two arrays and one word come back
+        auto& D = e->ndir;
+        auto& G = e->ing;
+        const auto t0 = clk::now();
+        ProfEvents<2> pev(e->iprof, st);  // KWOK_INGEST_PROF: everything of the call behind the echo filter
+        pev.stamp(0);
+        if (nd) {
+            launch_nd_lookup_frames(e->S, D.dir(), B, F, E.hdrop, st);
+            HIPCHK(e, hipGetLastError());
+        }
+        if (nk && (rc = nodes_framed_dev_impl(e, c, E.kidx, nk, n_host)) < 0) return rc;
+        HIPCHK(e, hipMemsetAsync(&D.call->rejected, 0, sizeof(D.call->rejected), st));
+        launch_nd_echo_fix(B, K, (uint32_t)nk, E.hdrop, G.out_handle, G.out_status, e->json.nstat, E.res_h, E.res_st,
+                           &D.call->rejected, st);
+        HIPCHK(e, hipGetLastError());
+        pev.stamp(1);
+        if (out_handles) HIPCHK(e, hipMemcpyAsync(out_handles, E.res_h, n * 4, hipMemcpyDeviceToHost, st));
+        if (out_status) HIPCHK(e, hipMemcpyAsync(out_status, E.res_st, n * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipMemcpyAsync(D.call_h, D.call, sizeof(*D.call_h.p), hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipStreamSynchronize(st));
+        if (pev.on())
+            fprintf(stderr, "[kwok nodes] %zu frames, %zu kept, %zu echoes: lookup + device-input ingest + merge %.3f ms on the device "
+                            "(host waits of the ingest included), %.3f ms wall; 8 bytes per record back\n", n, nk, nd, pev.elapsed(0, 1),
+                    ms_between(t0, clk::now()));
+        if (n_echoes) *n_echoes = nd;
+        return (int)D.call_h->rejected;
+    }
     // the node ingest takes its records from the host: the kept indices come back (4 bytes per kept
     // record), with every record's answer (1 byte) and, if any, the echoes' handles
     std::vector<uint32_t> kidx(nk), kpos(n);
@@ -3431,7 +3586,9 @@ int refs_query(kwok_engine* e, const char* who, const int32_t* handles, size_t f
     const auto t0 = clk::now();
     ProfEvents<5> pev(e->iprof, e->st);
     pev.stamp(0);
-    launch_refs_size(e->S, e->ref_dir(), Q, R.q_slot, st);
+    const bool nd = !pods && e->ndir.on;  // node queries with the node uid directory on: the uid behind the name
+    if (nd) launch_refs_size_nd(e->S, e->ref_dir(), e->ndir.dir(), Q, R.q_slot, st);
+    else launch_refs_size(e->S, e->ref_dir(), Q, R.q_slot, st);
     pev.stamp(1);
     HIPCHK(e, hipGetLastError());
     if (launch_refs_scan(Q, R.q_tmp, R.tmp_bytes, st)) return e->fail(KWOK_EDEVICE, "%s: scan", who);
@@ -3447,7 +3604,8 @@ int refs_query(kwok_engine* e, const char* who, const int32_t* handles, size_t f
     if ((rc = R.blob.reserve(e, total))) return rc;
     Q.blob = R.q_blob;
     pev.stamp(3);
-    launch_refs_gather(e->S, e->ref_dir(), Q, R.q_slot, st);
+    if (nd) launch_refs_gather_nd(e->S, e->ndir.dir(), Q, R.q_slot, st);
+    else launch_refs_gather(e->S, e->ref_dir(), Q, R.q_slot, st);
     pev.stamp(4);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipMemcpyAsync(refs, R.q_refs, n * sizeof(kwok_ref), hipMemcpyDeviceToHost, st));
@@ -3579,6 +3737,123 @@ int kwok_refs_stats(kwok_engine* e, uint64_t out[KWOK_REFS_STAT_COUNT]) {
     out[KWOK_REFS_STAT_BYTES] = (uint64_t)e->PLa * (KWOK_REF_STRIDE + sizeof(uint16_t)) + sizeof(RefCounters) +
                                 (uint64_t)R.items.cap * (8 + 8 + 4 + sizeof(kwok_ref)) + R.tmp_bytes + R.blob.cap +
                                 (uint64_t)R.spans.cap * (2 * 8 + 2 * 4 + 4) + R.arena.cap;
+    return KWOK_OK;
+}
+
+// ---- the node uid directory (kwok_watch.h, nodes.hip) ----------------------------------
+namespace {
+int ndir_read_counters(kwok_engine* e) {
+    auto& D = e->ndir;
+    HIPCHK(e, hipMemcpyAsync(D.ctr_h, D.ctr, sizeof(NodeDirCounters), hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    return KWOK_OK;
+}
+// kwok_node_lookup / kwok_node_bind: the spans whose length is 1..max_len and the caller's bytes they name, on the device
+int ndir_upload(kwok_engine* e, const int32_t* handles, const char* arena, const uint64_t* off, const uint32_t* len, size_t n,
+                uint32_t max_len, uint64_t* arena_len) {
+    auto& D = e->ndir;
+    uint64_t al = 0;
+    for (size_t i = 0; i < n; i++)  // (a span past 2^40 is the caller's error: it names no byte here and answers as a miss)
+        if (len[i] && len[i] <= max_len && off[i] < (1ull << 40)) al = std::max<uint64_t>(al, off[i] + len[i]);
+    if (al && !arena) return KWOK_EINVAL;
+    int rc = 0;
+    if ((rc = D.spans.reserve(e, n)) || (rc = D.arena.reserve(e, al + 1, grown(al) + 1))) return rc;
+    hipStream_t st = e->st;
+    if (handles) HIPCHK(e, hipMemcpyAsync(D.q_h, handles, n * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(D.q_off, off, n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemcpyAsync(D.q_len, len, n * 4, hipMemcpyHostToDevice, st));
+    if (al) HIPCHK(e, hipMemcpyAsync(D.q_arena, arena, al, hipMemcpyHostToDevice, st));
+    *arena_len = al;
+    return KWOK_OK;
+}
+}  // namespace
+
+int kwok_node_dir_enable(kwok_engine* e) {
+    if (!e) return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    if (e->multi) return e->fail(KWOK_EINVAL, "kwok_node_dir_enable: single-rank engines only");
+    auto& D = e->ndir;
+    if (D.on) return KWOK_OK;
+    drain(e);
+    if (e->poisoned) return poisoned(e);
+    int rc = 0;  // (dalloc zeroes: no node has a uid)
+    // (each piece on its own: a call that failed half way is finished by the next one)
+    if (!D.ctr && (rc = dalloc(e, &D.ctr, 1))) return rc;
+    if (!D.call && (rc = dalloc(e, &D.call, 1))) return rc;
+    if (!D.ctr_h) {
+        if (hipHostMalloc((void**)&D.ctr_h.p, sizeof(NodeDirCounters), hipHostMallocDefault) != hipSuccess)
+            return e->fail(KWOK_ENOMEM, "node directory staging");
+        memset(D.ctr_h, 0, sizeof(NodeDirCounters));
+    }
+    if (!D.call_h) {
+        if (hipHostMalloc((void**)&D.call_h.p, sizeof(*D.call_h.p), hipHostMallocDefault) != hipSuccess)
+            return e->fail(KWOK_ENOMEM, "node directory staging");
+        memset(D.call_h, 0, sizeof(*D.call_h.p));
+    }
+    if (!D.node_uid && (rc = dalloc(e, &D.node_uid, e->NL))) return rc;
+    if (!D.node_uid_key && (rc = dalloc(e, &D.node_uid_key, e->NL))) return rc;
+    if (!D.node_uid_len && (rc = dalloc(e, &D.node_uid_len, (size_t)e->NL + 4))) return rc;
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    D.on = true;
+    return KWOK_OK;
+}
+
+int kwok_node_lookup(kwok_engine* e, const char* arena, const uint64_t* off, const uint32_t* len, size_t n,
+                     int32_t* out_handles) {
+    if (!e || (n && (!off || !len || !out_handles)) || n > 0x07FFFFF0ull) return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    drain(e);  // (a name is judged against the state after every submitted tick)
+    if (e->poisoned) return poisoned(e);
+    if (!n) return KWOK_OK;
+    auto& D = e->ndir;
+    uint64_t al = 0;
+    int rc = ndir_upload(e, nullptr, arena, off, len, n, NODE_NAME_MAX, &al);
+    if (rc) return rc;
+    hipStream_t st = e->st;
+    launch_nd_lookup(e->S, D.on ? D.ctr.p : nullptr, D.q_arena, al, D.q_off, D.q_len, (uint32_t)n, D.q_h, st);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(out_handles, D.q_h, n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    return KWOK_OK;
+}
+
+int kwok_node_bind(kwok_engine* e, const int32_t* handles, const char* arena, const uint64_t* off, const uint32_t* len,
+                   size_t n, size_t* n_bad) {
+    if (n_bad) *n_bad = 0;
+    if (!e || (n && (!handles || !off || !len)) || n > 0x0FFFFFF0ull) return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    auto& D = e->ndir;
+    if (!D.on) return e->fail(KWOK_EINVAL, "kwok_node_bind: the node directory is not enabled");
+    drain(e);  // (a handle is judged against the state after every submitted tick)
+    if (e->poisoned) return poisoned(e);
+    if (!n) return KWOK_OK;
+    uint64_t al = 0;
+    int rc = ndir_upload(e, handles, arena, off, len, n, KWOK_UID_MAX, &al);
+    if (rc) return rc;
+    if (e->refs.on) e->refs.gen[KWOK_KIND_NODES]++;  // (kwok_read_refs' stale guard: a node's answer changes)
+    hipStream_t st = e->st;
+    HIPCHK(e, hipMemsetAsync(&D.ctr->bad, 0, sizeof(D.ctr->bad), st));
+    launch_nd_uid_bind(e->S, D.dir(), D.q_h, D.q_arena, al, D.q_off, D.q_len, (uint32_t)n, st);
+    HIPCHK(e, hipGetLastError());
+    if ((rc = ndir_read_counters(e))) return rc;
+    if (n_bad) *n_bad = (size_t)D.ctr_h->bad;
+    return KWOK_OK;
+}
+
+int kwok_node_dir_stats(kwok_engine* e, uint64_t out[KWOK_NODE_DIR_STAT_COUNT]) {
+    if (!e || !out) return KWOK_EINVAL;
+    auto& D = e->ndir;
+    for (int k = 0; k < KWOK_NODE_DIR_STAT_COUNT; k++) out[k] = 0;
+    if (!D.on) return KWOK_OK;
+    if (!e->poisoned)
+        if (int rc = ndir_read_counters(e)) return rc;
+    out[KWOK_NODE_DIR_STAT_LOOKUPS] = D.ctr_h->lookups;
+    out[KWOK_NODE_DIR_STAT_HITS] = D.ctr_h->hits;
+    out[KWOK_NODE_DIR_STAT_NOTES] = D.ctr_h->notes;
+    out[KWOK_NODE_DIR_STAT_BINDS] = D.ctr_h->binds;
+    out[KWOK_NODE_DIR_STAT_UNBOUND] = D.ctr_h->unbound;
+    out[KWOK_NODE_DIR_STAT_BYTES] = (uint64_t)e->NL * (KWOK_UID_MAX + 1 + 8) + 4 + sizeof(NodeDirCounters) + sizeof(*D.call_h.p) +
+                                    (uint64_t)D.spans.cap * (4 + 8 + 4) + D.arena.cap + (uint64_t)D.recs.cap * (4 + 4 + 1 + 4);
     return KWOK_OK;
 }
 

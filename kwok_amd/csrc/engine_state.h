@@ -368,6 +368,43 @@ struct kwok_engine {
                       uid.pod_uid_len, refs.ctr};
     }
 
+    // ---- the node uid directory (nodes.hip, kwok_watch.h): a uid per node slot (NL is fixed at create:
+    // nothing re-lays out node slots), the per-call buffers of lookup / bind and of a framed batch's uid spans ----
+    struct KWOK_LOCAL NodeDir {
+        struct Bytes {
+            uint8_t b[KWOK_UID_MAX];
+        };
+        bool on = false;
+        DevArr<Bytes> node_uid;           // [NL]
+        DevArr<uint8_t> node_uid_len;     // [NL + 4] (read by aligned words)
+        DevArr<uint64_t> node_uid_key;    // [NL]
+        DevArr<NodeDirCounters> ctr;
+        Pinned<NodeDirCounters> ctr_h;
+        // the device-input ingest's words of a call: the error word (a bad kept index), the rejected records
+        struct CallWords {
+            unsigned long long rejected;
+            uint32_t err, pad;
+        };
+        DevArr<CallWords> call;
+        Pinned<CallWords> call_h;
+        // lookup / bind: handles or results, spans, the caller's arena (kwok_node_lookup: also with the directory off)
+        DevArr<int32_t> q_h;
+        DevArr<uint64_t> q_off;
+        DevArr<uint32_t> q_len;
+        DevGroup spans{4096, {q_h, q_off, q_len}};
+        DevArr<uint8_t> q_arena;
+        DevGroup arena{1 << 16, {q_arena}};
+        // a framed node batch: its frame indices (an upload of the caller's), its records' uid spans in the resident
+        // stream, the host codec's statuses of the documents it decided
+        DevArr<uint32_t> fidx, uoff;
+        DevArr<uint8_t> ulen;
+        DevArr<int32_t> hstat;
+        DevGroup recs{4096, {fidx, uoff, ulen, hstat}};
+        // the framed batch whose records the node ingest is applying (null: an entry that carries no uid)
+        const NodeUidNote* note = nullptr;
+        NodeDirX dir() const { return NodeDirX{reinterpret_cast<uint8_t*>(node_uid.p), node_uid_len, node_uid_key, ctr}; }
+    } ndir;
+
     // ---- the pod codec on the GPU (json.hip): per-document buffers, the codec's
     // selectors, the spec table (kwok_spec_key -> spec id) ----
     struct KWOK_LOCAL Json {

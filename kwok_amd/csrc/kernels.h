@@ -505,4 +505,54 @@ size_t refs_scan_bytes(uint32_t n);
 int launch_refs_scan(const RefQuery& Q, void* tmp, size_t tmp_bytes, hipStream_t st);
 void launch_refs_gather(const DevState& S, const RefDir& R, const RefQuery& Q, const uint32_t* slots, hipStream_t st);
 
+// ---- the node uid directory (nodes.hip, kwok_watch.h): a uid per node slot, names -> handles in batches ----
+// (kept out of DevState, beside UidDir / RefDir: only nodes.hip and the node forms of the reference kernels see it)
+struct NodeDirCounters {  // device memory, read back by the host
+    unsigned long long lookups, hits, notes, binds, unbound;
+    unsigned long long bad;  // kwok_node_bind: records that stored nothing (reset per call)
+};
+constexpr uint8_t ND_STALE = 0x80;     // node_uid_len: the node was deleted; its bytes stay until the slot is created into
+constexpr uint8_t ND_LEN_MASK = 0x3F;  // ... and the uid's length
+constexpr uint8_t ND_NO_UID = 0x3F;    // ... or: a node recorded without a uid (its later upserts are no creates)
+struct NodeDirX {
+    uint8_t* node_uid;      // [NL][KWOK_UID_MAX] (the node slot count is fixed at create: never re-laid out)
+    uint8_t* node_uid_len;  // [NL] length | ND_STALE; 0: nothing recorded
+    uint64_t* node_uid_key; // [NL] node_key of the entry the slot's uid was stored for
+    NodeDirCounters* ctr;
+};
+// the uids of the node batch the ingest is applying, per record (ulen null: the entry carries none)
+struct NodeUidNote {
+    const uint8_t* stream;  // the resident stream
+    uint64_t stream_len;
+    const uint32_t* uoff;   // [n] the record's uid span; ulen 0: none the device can store exactly
+    const uint8_t* ulen;
+};
+// 16 lanes x 8-byte keys: one step of a group reads one 128-byte line of its bucket's node_key words, a
+// 64-slot bucket takes four steps; 8 lanes would leave half of every line to a second request
+constexpr uint32_t ND_LOOKUP_LANES = 16;
+constexpr uint32_t ND_BIND_LANES = 8;  // lanes per item of k_nd_uid_bind, 8 bytes each
+struct EchoBatch;
+struct EchoFrames;
+// out[i]: the existing node named arena[off[i], +len[i]), or -1 (ctr null: nothing is counted)
+void launch_nd_lookup(const DevState& S, NodeDirCounters* ctr, const uint8_t* arena, uint64_t arena_len, const uint64_t* off,
+                      const uint32_t* len, uint32_t n, int32_t* out, hipStream_t st);
+// a dropped node frame's handle (k_echo_node_handles' answers by the grouped lookup)
+void launch_nd_lookup_frames(const DevState& S, const NodeDirX& D, const EchoBatch& B, const EchoFrames& F, int32_t* hdrop,
+                             hipStream_t st);
+// behind the last apply pass of a node batch
+void launch_nd_uid_note(const DevState& S, const NodeBatch& N, const NodeDirX& D, const NodeUidNote& U, hipStream_t st);
+void launch_nd_uid_bind(const DevState& S, const NodeDirX& D, const int32_t* handles, const uint8_t* arena, uint64_t arena_len,
+                        const uint64_t* off, const uint32_t* len, uint32_t n, hipStream_t st);
+// the device-input node ingest (k_nd_frame_recs, k_nd_stat_scatter, k_nd_echo_fix: nodes.hip)
+struct EchoKeep;
+void launch_nd_frame_recs(const kwok_watch_frame* frames, uint32_t n_frames, uint64_t stream_len, const uint32_t* idx, uint32_t n,
+                          bool strict, uint64_t* off, uint32_t* len, uint8_t* op, uint32_t* uoff, uint8_t* ulen, uint32_t* err,
+                          hipStream_t st);
+void launch_nd_stat_scatter(int32_t* nstat, const uint32_t* list, const int32_t* vals, uint32_t n, hipStream_t st);
+void launch_nd_echo_fix(const EchoBatch& B, const EchoKeep& K, uint32_t nk, const int32_t* hdrop, const int32_t* h, const int32_t* status,
+                        const int32_t* nstat, int32_t* out_h, int32_t* out_status, unsigned long long* rejected, hipStream_t st);
+// the node forms of launch_refs_size / launch_refs_gather with the node directory on: the uid behind the name
+void launch_refs_size_nd(const DevState& S, const RefDir& R, const NodeDirX& D, const RefQuery& Q, uint32_t* slots, hipStream_t st);
+void launch_refs_gather_nd(const DevState& S, const NodeDirX& D, const RefQuery& Q, const uint32_t* slots, hipStream_t st);
+
 }  // namespace kwok

@@ -19,6 +19,9 @@
 //   k_refs_gather  REF_GATHER_LANES lanes per item: only the units the lengths say are in
 //                  use, 16-byte loads of the record, 8-byte loads of the uid, aligned
 //                  16-byte stores of the item; the group's first lane writes refs[i]
+//   k_refs_size_nd / k_refs_gather_nd  the two above for node queries while the node uid directory
+//                  (nodes.hip) is on: the uid behind the name, from node_uid (stride
+//                  40) and node_uid_len (length | ND_STALE)
 //
 // Every loop is bounded by a constant; no block waits on another; no kernel indexes a
 // local array dynamically (no scratch).  The kernels that count (notes, binds, reads) add
@@ -228,10 +231,88 @@ __global__ __launch_bounds__(256) void k_refs_gather(DevState S, RefDir R, RefQu
     if (sub == 0) reinterpret_cast<uint4*>(Q.refs)[i] = make_uint4((uint32_t)off, (uint32_t)(off >> 32), packed, 0u);
 }
 
+// ---- node queries with the node uid directory on: the uid behind the name.  Kernels of their
+// own, so that k_refs_size / k_refs_gather (pods, and nodes with the directory off) stay what they were ----
+__global__ __launch_bounds__(COUNT_BLOCK) void k_refs_size_nd(DevState S, RefDir R, NodeDirX D, RefQuery Q, uint32_t* slots) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool read = false, missing = false;
+    if (i < Q.n) {
+        const int32_t h = Q.handles[Q.first + i];
+        uint32_t slot = 0, nl = 0, ul = 0;
+        int32_t status = KWOK_ENOTFOUND;
+        const int64_t s = (int64_t)h - S.node_handle_base;
+        if (s >= 0 && s < (int64_t)S.n_node_slots) {
+            slot = (uint32_t)s;
+            const uint64_t key = S.node_key[slot];
+            const uint32_t lb = D.node_uid_len[slot];
+            // a stale uid (its node was deleted) is what the slot last stored: KWOK_REFS_ANY_SLOT alone answers it
+            const uint32_t ln = lb & (uint32_t)ND_LEN_MASK;
+            // ... and only of the entry it was stored for: a placeholder made in a freed slot is another node
+            const bool own = !key || D.node_uid_key[slot] == key;
+            const uint32_t stored = own && ln != ND_NO_UID && (Q.any_slot || !(lb & ND_STALE)) ? min(ln, (uint32_t)KWOK_UID_MAX) : 0u;
+            if (key && (Q.any_slot || (S.node_state[slot] & NS_SLOT))) {
+                nl = min((uint32_t)(key >> 32), NODE_NAME_MAX);
+                status = nl ? KWOK_OK : KWOK_ENOTFOUND;
+                ul = nl ? stored : 0u;
+            } else if (!key && Q.any_slot && stored) {  // the entry is gone, its uid bytes remain
+                status = KWOK_REF_NONE;
+                ul = stored;
+            }
+        }
+        reinterpret_cast<uint4*>(Q.refs)[i] = make_uint4(0u, 0u, (nl << 8) | (ul << 16) | ((uint32_t)(uint8_t)status << 24), 0u);
+        Q.len[i] = (uint64_t)((nl + ul + 15u) & ~15u);
+        slots[i] = slot;
+        read = true;
+        missing = status == KWOK_ENOTFOUND;
+    }
+    block_add(read, &R.ctr->reads);
+    block_add(missing, &R.ctr->not_found);
+}
+
+__global__ __launch_bounds__(256) void k_refs_gather_nd(DevState S, NodeDirX D, RefQuery Q, const uint32_t* slots) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t i = (uint32_t)(t / REF_GATHER_LANES), sub = (uint32_t)(t % REF_GATHER_LANES);
+    if (i >= Q.n) return;
+    const uint32_t packed = reinterpret_cast<const uint4*>(Q.refs)[i].z;  // name_len << 8 | uid_len << 16 | status << 24
+    const uint64_t off = Q.off[i];
+    const uint32_t slot = slots[i];
+    const uint32_t a = (packed >> 8) & 255u, ul = (packed >> 16) & 255u, units = (a + ul + 15u) >> 4;
+    const uint8_t* rec = S.node_name + (size_t)slot * NAME_STRIDE;
+    const uint8_t* uid = D.node_uid + (size_t)slot * KWOK_UID_MAX;
+    uint4* dst = reinterpret_cast<uint4*>(Q.blob + off);
+#pragma unroll
+    for (uint32_t k = 0; k < GATHER_STEPS; k++) {
+        const uint32_t u = sub + k * REF_GATHER_LANES;
+        if (u >= units || u >= ITEM_UNITS) continue;
+        uint64_t lo = 0, hi = 0;
+        if (16u * u < a) {  // bytes of the name: the unit, cut at its end
+            const uint4 v = reinterpret_cast<const uint4*>(rec)[u];
+            lo = v.x | ((uint64_t)v.y << 32), hi = v.z | ((uint64_t)v.w << 32);
+            const uint32_t rem = a - 16u * u;
+            if (rem <= 8) hi = 0;
+            if (rem < 8) lo &= (1ull << (rem * 8u)) - 1ull;
+            else if (rem > 8 && rem < 16) hi &= (1ull << ((rem - 8u) * 8u)) - 1ull;
+        }
+        if (ul && 16u * u + 16u > a) {  // bytes of the uid, which starts at byte a of the item
+            const int32_t o = (int32_t)(16u * u) - (int32_t)a;
+            lo |= uid_at(uid, ul, o), hi |= uid_at(uid, ul, o + 8);
+        }
+        dst[u] = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+    }
+    if (sub == 0) reinterpret_cast<uint4*>(Q.refs)[i] = make_uint4((uint32_t)off, (uint32_t)(off >> 32), packed, 0u);
+}
+
 inline uint32_t cdiv(uint64_t a, uint64_t b) { return (uint32_t)((a + b - 1) / b); }
 
 }  // namespace
 
+void launch_refs_size_nd(const DevState& S, const RefDir& R, const NodeDirX& D, const RefQuery& Q, uint32_t* slots, hipStream_t st) {
+    if (Q.n) hipLaunchKernelGGL(k_refs_size_nd, dim3(cdiv(Q.n, COUNT_BLOCK)), dim3(COUNT_BLOCK), 0, st, S, R, D, Q, slots);
+}
+void launch_refs_gather_nd(const DevState& S, const NodeDirX& D, const RefQuery& Q, const uint32_t* slots, hipStream_t st) {
+    if (Q.n)
+        hipLaunchKernelGGL(k_refs_gather_nd, dim3(cdiv((uint64_t)Q.n * REF_GATHER_LANES, 256)), dim3(256), 0, st, S, D, Q, slots);
+}
 void launch_refs_note(const DevState& S, const IngestBatch& I, const RefDir& R, const RefNote& N, hipStream_t st) {
     if (I.n)
         hipLaunchKernelGGL(k_refs_note, dim3(cdiv((uint64_t)I.n * REF_NOTE_LANES, COUNT_BLOCK)), dim3(COUNT_BLOCK), 0, st, S, I, R, N);

@@ -141,6 +141,10 @@ def declare(lib, pre):
             "refs_lookup": (C.c_int, [VP, C.c_int, VP, SZ, U32, VP, VP, SZ, P(SZ)]),
             "read_refs": (C.c_int, [VP, C.c_int, SZ, SZ, VP, VP, SZ, P(SZ)]),
             "refs_stats": (C.c_int, [VP, VP]),
+            "node_dir_enable": (C.c_int, [VP]),
+            "node_lookup": (C.c_int, [VP, VP, VP, VP, SZ, VP]),
+            "node_bind": (C.c_int, [VP, VP, VP, VP, VP, SZ, P(SZ)]),
+            "node_dir_stats": (C.c_int, [VP, VP]),
         })
     for name, (res, args) in sig.items():
         f = getattr(lib, pre + name, None)
@@ -914,6 +918,39 @@ class Engine(EngineBase):
         out = (C.c_uint64 * len(abi.REFS_STATS))()
         self._check(self._lib.kwok_refs_stats(self._h, out), "refs_stats")
         return dict(zip(abi.REFS_STATS, list(out)))
+
+    # ---- the node uid directory (include/kwok_watch.h): a uid per node slot, names -> handles in batches ----
+    def node_dir_enable(self):
+        """kwok_node_dir_enable: allocate the directory (idempotent; single-rank engines only)"""
+        self._check(self._lib.kwok_node_dir_enable(self._h), "node_dir_enable")
+
+    def node_lookup(self, names):
+        """kwok_node_lookup: the handle of the existing node of each name (bytes or str), or -1; needs no
+        directory enabled"""
+        arena, offs, lens = self._uid_spans(names)
+        out = np.empty(len(lens), np.int32)
+        rc = self._lib.kwok_node_lookup(self._h, arena.ctypes.data, offs.ctypes.data, lens.ctypes.data, len(lens),
+                                        out.ctypes.data)
+        self._check(rc, "node_lookup")
+        return out
+
+    def node_bind(self, handles, uids):
+        """kwok_node_bind: uids[i] becomes the uid of existing node handles[i] -> the records that stored nothing"""
+        hs = np.ascontiguousarray(handles, np.int32)
+        arena, offs, lens = self._uid_spans(uids)
+        assert len(hs) == len(lens)
+        bad = C.c_size_t()
+        rc = self._lib.kwok_node_bind(self._h, hs.ctypes.data, arena.ctypes.data, offs.ctypes.data, lens.ctypes.data, len(hs),
+                                      C.byref(bad))
+        self._check(rc, "node_bind")
+        return bad.value
+
+    def node_dir_stats(self):
+        """kwok_node_dir_stats: names probed / resolved, uids stored by ingests / by binds, records stored without
+        a uid, device bytes held (all zero while the directory is off)"""
+        out = (C.c_uint64 * len(abi.NODE_DIR_STATS))()
+        self._check(self._lib.kwok_node_dir_stats(self._h, out), "node_dir_stats")
+        return dict(zip(abi.NODE_DIR_STATS, list(out)))
 
     @staticmethod
     def _arena_arg(arena):
