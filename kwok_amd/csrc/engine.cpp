@@ -743,6 +743,7 @@ int kwok_engine_create(const kwok_config* cfg, kwok_engine** out) {
         if (const char* v = getenv("KWOK_TICK_STREAM_DELAY_NS")) S.stream_delay = (uint32_t)std::max(0, atoi(v) / 10);
         if (const char* v = getenv("KWOK_TICK_STREAM_SHARE")) e->share_env = std::min(1024, std::max(0, atoi(v)));
         if (const char* v = getenv("KWOK_HB_NT")) e->nt_env = atoi(v) != 0;
+        if (const char* v = getenv("KWOK_HB_KEEP")) e->keep_env = std::min(64, std::max(0, atoi(v)));
         if (const char* v = getenv("KWOK_HB_DELTA")) e->hb_delta = atoi(v) != 0;
         if (const char* v = getenv("KWOK_DEBUG_LAYOUT_FAULT_TICK")) e->debug_fault_tick = strtoull(v, nullptr, 10);
         if (const char* v = getenv("KWOK_DEBUG_INGEST_FAIL_CHUNK")) e->debug_fail_chunk = (uint32_t)strtoul(v, nullptr, 10);

@@ -638,6 +638,8 @@ struct kwok_engine {
     bool hb_delta = true;       // KWOK_HB_DELTA=0: every tick writes the whole heartbeat stream (A/B, tests)
     uint32_t hb_gen = 0;        // heartbeat template generation (bumped by every upload of the template or `start`)
     int nt_env = -1;            // KWOK_HB_NT (0 / 1: heartbeat stores plain / non-temporal), else automatic
+    int keep_env = -1;          // KWOK_HB_KEEP (0..64 of every 64 groups of a non-temporal delta stream stored plain), else
+                                // automatic: HB_KEEP_BUDGET's share on the quiet ticks of a region past the Infinity Cache
     int share_env = -1;         // KWOK_TICK_STREAM_SHARE (/1024 of the stream to the streamer blocks), else automatic
     uint32_t tick_tag = 0;      // nonzero id of the last FRONT launch
     uint64_t front_launches = 0;  // FRONT launches since the cross-block state was last zeroed

@@ -234,6 +234,26 @@ int enqueue_tick(kwok_engine* e, int k, bool requeue) {
         T.count_reused = T.once_stream && !requeue && !fault_tick && e->count_reuse_ok && C.ok && C.gen == e->state_gen &&
                          C.tot[AG_HB] == nhb && L.ok && L.list == T.hb_nodes && L.n == nhb && L.gen == e->state_gen;
     }
+    // a non-temporal delta stream keeps a share of its lines in the Infinity Cache: the dirty
+    // lines of a slot are the same addresses tick after tick, so hb_keep of every 64 groups are
+    // stored plain and overwritten on die, and HBM takes the rest (all plain
+    // cycles both slots' lines through the cache and keeps none).  The share is what fits
+    // HB_KEEP_BUDGET over the allocated slots' dirty lines: one slot (blocking ticks) holds
+    // twice the share of two.  On the quiet ticks (k_hb_stream, k_once_stream); a k_tick delta
+    // tick, whose classification reads share that cache, stays all non-temporal until its own
+    // A/B is repeated (one C4 run with the share forced was faster).
+    // KWOK_HB_KEEP forces a value on every delta tick (A/B, tests; 0: no share)
+    S.hb_keep = 0;
+    if (T.hb_prev && S.hb_nt) {
+        if (e->keep_env >= 0) {
+            S.hb_keep = (uint32_t)e->keep_env;
+        } else if (T.once && hb_bytes >= (256ull << 20)) {
+            const double lines = hb_dirty_lines_per_body(e->hb_tpl.now_slots.data(), e->hb_tpl.now_slots.size(), S.hb_units,
+                                                         T.hb_prev, T.now);
+            const double dirty = ((e->slots[0].alloc ? 1 : 0) + (e->slots[1].alloc ? 1 : 0)) * (double)nhb * lines * 64.0;
+            S.hb_keep = dirty > 0 ? (uint32_t)std::min(64.0, 64.0 * (double)HB_KEEP_BUDGET / dirty) : 0u;
+        }
+    }
     // (k_once_stream's counting blocks are done in ~10 us: the stream is the streamers')
     S.stream_share = e->n_stream == 0 ? 0u
                      : T.count_reused  ? 1024u  // (nobody else to write a tail)

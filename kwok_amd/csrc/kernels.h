@@ -123,6 +123,9 @@ struct DevState {
     // heartbeat geometry (default: HB_STRIDE / 16, HB_PREFIX, CONDS_LEN; a custom template's otherwise)
     uint32_t hb_units;         // 16-byte units per heartbeat slot (arena stride = 16 x hb_units)
     uint32_t conds_off, conds_len;  // the conditions list inside the heartbeat (spliced into node inits)
+    // (last: no other field's offset moves, and the kernels that never read it keep their code)
+    uint32_t hb_keep;          // delta stream with hb_nt: groups with (g & 63) < hb_keep are stored plain and stay in
+                               // the Infinity Cache, the others non-temporal (0..64, uniform; 0: all non-temporal)
 };
 
 __device__ __host__ inline int32_t pod_handle_of(const DevState& S, uint32_t slot) {

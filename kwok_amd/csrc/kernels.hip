@@ -1715,6 +1715,28 @@ __device__ __forceinline__ void hb_fill_delta(const DevState& S, const uint4* tm
     uint64_t g = g0 + t / n_e;
     uint32_t r = t % n_e;
     const bool nt = S.hb_nt != 0;
+    // a resident share (S.hb_keep of every 64 groups, by the group's index alone: the same
+    // lines on every tick, whatever the split or n_e) is stored plain and is overwritten
+    // in the Infinity Cache tick after tick; the rest streams past it non-temporally.
+    // The two stores are spelled as instructions: as C++ stores under one condition the
+    // compiler merges them into a single plain store (tools/micro/fill_sparse.hip).
+    const uint32_t keep = nt ? S.hb_keep : 0u;
+    if (keep) {
+        while (g < g1) {
+            const uint32_t it = D->item[r];
+            const uint64_t i = g * GU + (it & 511u);
+            if (i < units) {
+                const uint4 v = tmpl[it >> 9];
+                const u32x4 x = u32x4{v.x, v.y, v.z, v.w};
+                if (((uint32_t)g & 63u) < keep) asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(dst + i), "v"(x) : "memory");
+                else asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(dst + i), "v"(x) : "memory");
+            }
+            g += dg;
+            r += dr;
+            if (r >= n_e) r -= n_e, g++;
+        }
+        return;
+    }
     while (g < g1) {
         const uint32_t it = D->item[r];
         const uint64_t i = g * GU + (it & 511u);

@@ -73,6 +73,18 @@ bool compile_node_template(const std::string& tpl, const std::string& addresses_
 std::string heartbeat_patch(const HeartbeatTemplate& hb, const std::string& now, const std::string& start);
 std::string heartbeat_conditions(const HeartbeatTemplate& hb, const std::string& now, const std::string& start);
 
+// The delta stream's dirty 64-byte lines per body between the bodies of two clocks: the
+// distinct lines of a 4-slot group (units whole lines) that hold a character of a Now
+// value that differs, divided by four - hb_fill_delta's marks (kernels.hip) on the host.
+// Exported for the tests as kwok_hb_dirty_lines (not part of the ABI).
+double hb_dirty_lines_per_body(const uint16_t* now_slots, size_t n_slots, uint32_t units, uint64_t prev_unix,
+                               uint64_t now_unix);
+// The bytes of delta-stream lines the Infinity Cache holds between ticks, over all tick
+// slots: the resident share of tools/micro/fill_sparse's fastest "l64 mixed k/64" row at two
+// alternating 320 MB passes, k = 24 (profiles/m1_fill_sparse.txt: 72.5 us a pass against
+// 91.3 all non-temporal; 264 MB resident, k = 24 of 352 MB passes, already loses to 176 MB)
+constexpr uint64_t HB_KEEP_BUDGET = 240000000ull;
+
 // k_emit's timestamp-slot lookup of a spec (false: layout outside what it handles)
 bool build_ts_lookup(const SpecProgram& p, std::vector<uint16_t>& out);
 // k_emit's unit tables of a spec (device.h, "table-driven pod path"):

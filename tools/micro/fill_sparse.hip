@@ -16,7 +16,13 @@
 // Last, the l64 pass once more with every cache-policy form of the 16-byte vector
 // store (global_store_dwordx4 with nt / sc0 / sc1 in each combination; sc0 sc1 is
 // the write-through, system-scope form), plain and nt among them as the run's own
-// reference.
+// reference.  After those, the l64 pass with an address-determined share of the
+// groups stored plain and the rest nt ("mixed k/64": group g plain iff
+// (g & 63) < k), on two alternating regions and on one, next to the plain nt
+// pass on each.
+// Every row has two timings: one event pair per pass with a synchronise between
+// passes, and "steady", one event pair around 24 passes back to back (per pass),
+// which is how queued ticks run.
 // usage: fill_sparse [n_hb] [--pmc]   (--pmc: 3 passes per variant and no timing,
 // for rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE; the variant is in the kernel name)
 // build: hipcc --offload-arch=gfx950 -O3 -I kwok_amd/csrc tools/micro/fill_sparse.hip
@@ -76,6 +82,38 @@ __global__ __launch_bounds__(256) void k_sparse(u32x4* dst, uint64_t n_hb, uint3
         if (i < units) {
             if (NT) __builtin_nontemporal_store(tmpl[u % U], dst + i);
             else dst[i] = tmpl[u % U];
+        }
+        g += dg;
+        r += dr;
+        if (r >= n_e) r -= n_e, g++;
+    }
+}
+
+// k_sparse's l64 walk with the policy a function of the group's address alone:
+// group g is resident iff (g & 63) < keep and is stored plain, every other group
+// non-temporal.  keep 0 is the nt pass, keep 64 the plain one.
+template <int SET, int BPC>
+__global__ __launch_bounds__(256) void k_mixed(u32x4* dst, uint64_t n_hb, uint32_t GS, const uint16_t* el_g, uint32_t n_e, uint32_t keep) {
+    __shared__ uint16_t el[MAX_E];
+    __shared__ u32x4 tmpl[U];
+    for (uint32_t i = threadIdx.x; i < n_e; i += blockDim.x) el[i] = el_g[i];
+    for (uint32_t i = threadIdx.x; i < U; i += blockDim.x) tmpl[i] = u32x4{i, 1u, 2u, 3u};
+    __syncthreads();
+    if (!n_e) return;
+    const uint64_t units = n_hb * U, GU = (uint64_t)GS * U;
+    const uint64_t ng = (n_hb + GS - 1) / GS, g0 = ng * blockIdx.x / gridDim.x, g1 = ng * (blockIdx.x + 1) / gridDim.x;
+    const uint32_t step = blockDim.x, dg = step / n_e, dr = step % n_e;
+    uint64_t g = g0 + threadIdx.x / n_e;
+    uint32_t r = threadIdx.x % n_e;
+    while (g < g1) {
+        const uint32_t u = el[r];
+        const uint64_t i = g * GU + u;
+        if (i < units) {
+            // spelled as instructions: written as two C++ stores under one
+            // condition, the compiler merges them into a single plain store
+            const u32x4 v = tmpl[u % U];
+            if (((uint32_t)g & 63u) < keep) asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(dst + i), "v"(v) : "memory");
+            else asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(dst + i), "v"(v) : "memory");
         }
         g += dg;
         r += dr;
@@ -168,28 +206,43 @@ int main(int argc, char** argv) {
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0);
     printf("n_hb %llu (%.1f MB per region, two regions alternating), %d CUs, blocks of 256\n", (unsigned long long)n_hb,
            n_hb * 1072 / 1e6, cus);
-    int pass = 0;
+    int pass = 0, regions = 2;  // regions 1: every pass rewrites dst[0] (one tick slot)
+    constexpr int STEADY_PASSES = 24, STEADY_REPEATS = 6;
     auto measure = [&](const char* name, double bytes, auto&& launch) {
         if (pmc) {
-            for (int r = 0; r < 3; r++) launch(dst[pass++ & 1]);
+            for (int r = 0; r < 3; r++) launch(dst[pass++ & (regions - 1)]);
             (void)hipDeviceSynchronize();
             printf("%s: %.1f MB stored per pass\n", name, bytes / 1e6);
             return;
         }
-        for (int w = 0; w < 4; w++) launch(dst[pass++ & 1]);
+        for (int w = 0; w < 4; w++) launch(dst[pass++ & (regions - 1)]);
         (void)hipDeviceSynchronize();
         float best = 1e9, worst = 0, sum = 0;
         for (int r = 0; r < 10; r++) {
             (void)hipEventRecord(e0);
-            launch(dst[pass++ & 1]);
+            launch(dst[pass++ & (regions - 1)]);
             (void)hipEventRecord(e1);
             (void)hipEventSynchronize(e1);
             float ms;
             (void)hipEventElapsedTime(&ms, e0, e1);
             best = std::min(best, ms), worst = std::max(worst, ms), sum += ms;
         }
-        printf("%-28s %7.1f MB/pass: best %7.1f mean %7.1f worst %7.1f us -> %.2f TB/s stored (best)\n", name, bytes / 1e6,
-               best * 1e3, sum * 1e2, worst * 1e3, bytes / (best * 1e-3) / 1e12);
+        // steady: the passes back to back in one event pair, as queued ticks run;
+        // the memory side does not drain between them
+        float sbest = 1e9, sworst = 0, ssum = 0;
+        for (int r = 0; r < STEADY_REPEATS; r++) {
+            (void)hipEventRecord(e0);
+            for (int p = 0; p < STEADY_PASSES; p++) launch(dst[pass++ & (regions - 1)]);
+            (void)hipEventRecord(e1);
+            (void)hipEventSynchronize(e1);
+            float ms;
+            (void)hipEventElapsedTime(&ms, e0, e1);
+            ms /= STEADY_PASSES;
+            sbest = std::min(sbest, ms), sworst = std::max(sworst, ms), ssum += ms;
+        }
+        printf("%-28s %7.1f MB/pass: best %7.1f mean %7.1f worst %7.1f us -> %.2f TB/s stored (best); steady best %7.1f mean %7.1f worst %7.1f us\n",
+               name, bytes / 1e6, best * 1e3, sum * 1e2, worst * 1e3, bytes / (best * 1e-3) / 1e12, sbest * 1e3,
+               ssum * 1e3 / STEADY_REPEATS, sworst * 1e3);
     };
     // both regions hold bodies before any sparse pass (and the yardstick: the full stream)
     for (int bpc : {1, 2}) {
@@ -247,5 +300,39 @@ int main(int argc, char** argv) {
                 });
             }
     }
+    // the l64 pass with k of every 64 groups stored plain (resident on die if the
+    // cache keeps them), the rest nt: two regions alternating (two tick slots) and
+    // one region (blocking ticks); k 0 is the nt pass and the row to beat.  The
+    // sweep runs twice, so a drift of the machine shows as a difference of rounds.
+    for (int round = 0; round < 2; round++)
+        for (regions = 2; regions >= 1; regions--)
+            for (int set = 0; set < 2; set++) {
+                const uint32_t GS = 4, GU = GS * U;
+                std::vector<uint16_t> el;
+                for (uint32_t p0 = 0; p0 < GU; p0 += 4) {
+                    bool d = false;
+                    for (uint32_t u = p0; u < p0 + 4; u++) d |= dirty[set][u % U];
+                    if (d)
+                        for (uint32_t u = p0; u < p0 + 4; u++) el.push_back((uint16_t)u);
+                }
+                if (hipMemcpy(el_d, el.data(), el.size() * 2, hipMemcpyHostToDevice) != hipSuccess) return 1;
+                const double bytes = (double)((n_hb + GS - 1) / GS) * el.size() * 16;
+                if (round == 0) {
+                    char name[64];
+                    snprintf(name, sizeof name, "set %d l64 nt %dreg b/CU 2", set, regions);
+                    sparse_fn fn = pick_p<1>(4, set, 2);
+                    measure(name, bytes, [&](u32x4* d) {
+                        hipLaunchKernelGGL(fn, dim3(cus * 2), dim3(256), 0, 0, d, n_hb, GS, el_d, (uint32_t)el.size());
+                    });
+                }
+                for (uint32_t k : {0u, 8u, 16u, 24u, 32u, 48u, 64u}) {
+                    char name[64];
+                    snprintf(name, sizeof name, "set %d l64 mixed %2u/64 %dreg r%d", set, k, regions, round);
+                    auto fn = set == 0 ? k_mixed<0, 2> : k_mixed<1, 2>;
+                    measure(name, bytes, [&](u32x4* d) {
+                        hipLaunchKernelGGL(fn, dim3(cus * 2), dim3(256), 0, 0, d, n_hb, GS, el_d, (uint32_t)el.size(), k);
+                    });
+                }
+            }
     return hipDeviceSynchronize() == hipSuccess ? 0 : 1;
 }
