@@ -618,7 +618,11 @@ int kwok_decode_pods(const kwok_codec* c, char* arena, size_t arena_len, const u
  *   handle of a known pod or -1, KWOK_OP_DELETE with its handle); a new pod's
  *   node by its spec.nodeName; pod specs are registered as they first appear
  *   (kwok_register_pod_spec).  A document that fails to decode gets its decode
- *   status in out_status and changes nothing.  Outputs as kwok_ingest_pods. */
+ *   status in out_status and changes nothing.  Outputs as kwok_ingest_pods.
+ * Both refuse an arena longer than KWOK_JSON_ARENA_MAX with KWOK_EINVAL before
+ * any byte is read (the scanner's positions and kwok_str offsets are 32 bits),
+ * as kwok_ingest_nodes_json and the framers do. */
+#define KWOK_JSON_ARENA_MAX 0xFFFFFFF0ull
 uint64_t kwok_spec_key(const kwok_pod_spec* spec, const char* arena, size_t arena_len);
 int kwok_decode_pods_gpu(kwok_engine* e, const kwok_codec* c, const char* arena, size_t arena_len,
                          const uint64_t* doc_off, const uint32_t* doc_len, size_t n, kwok_pod_event* ev,

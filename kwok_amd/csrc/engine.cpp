@@ -1873,7 +1873,12 @@ int json_complete(kwok_engine* e, const kwok_codec* c, const char* arena, size_t
     std::unordered_map<std::pair<uint64_t, uint64_t>, int32_t, K2Hash> fresh;
     char* ar = const_cast<char*>(arena);  // (kwok_decode_pod writes only node blobs)
     kwok_pod_doc d;
-    for (uint32_t q = 0; q < nh; q++) {
+    // in document order (the device wrote the list in the order its atomics landed): spec ids, and which
+    // documents meet KWOK_EFULL, are then those of the host path; the scatter takes any order
+    std::vector<uint32_t> order(nh);
+    for (uint32_t q = 0; q < nh; q++) order[q] = q;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return list[a] < list[b]; });
+    for (uint32_t q : order) {
         const uint32_t i = list[q];
         JsonPodSide& s = side[q];
         const bool ups = !op || op[i] == KWOK_OP_UPSERT;
@@ -1901,9 +1906,13 @@ int json_complete(kwok_engine* e, const kwok_codec* c, const char* arena, size_t
             s.spec_key = kwok_spec_key(&sp, arena, arena_len);
             if (op && ups) {
                 const int r2 = kwok_register_pod_spec(e, &sp, arena, arena_len, &id);
-                if (r2 == KWOK_OK && miss) fresh[dkey] = id;
-                else if (r2 == KWOK_EDOMAIN || r2 == KWOK_EFULL) rc = r2;  // the spec is outside the domain
-                else return r2;
+                if (r2 == KWOK_OK) {
+                    if (miss) fresh[dkey] = id;
+                } else if (r2 == KWOK_EDOMAIN || r2 == KWOK_EFULL) {
+                    rc = r2;  // the spec is outside the domain
+                } else {
+                    return r2;
+                }
             }
         }
         if (op) {
@@ -2189,7 +2198,8 @@ int kwok_decode_nodes_gpu(kwok_engine* e, const kwok_codec* c, char* arena, size
 int kwok_decode_pods_gpu(kwok_engine* e, const kwok_codec* c, const char* arena, size_t arena_len,
                          const uint64_t* doc_off, const uint32_t* doc_len, size_t n, kwok_pod_event* ev,
                          kwok_str* name_ns, uint64_t* spec_key, int32_t* status, size_t* n_host) {
-    if (!e || !c || (n && (!doc_off || !doc_len || !ev || !status)) || (arena_len && !arena) || n > 0x7FFFFFF0ull)
+    if (!e || !c || (n && (!doc_off || !doc_len || !ev || !status)) || (arena_len && !arena) || n > 0x7FFFFFF0ull ||
+        arena_len > KWOK_JSON_ARENA_MAX)
         return KWOK_EINVAL;
     if (e->poisoned) return poisoned(e);
     drain(e);
@@ -2224,7 +2234,8 @@ int kwok_decode_pods_gpu(kwok_engine* e, const kwok_codec* c, const char* arena,
 int kwok_ingest_pods_json(kwok_engine* e, const kwok_codec* c, const char* arena, size_t arena_len,
                           const uint64_t* doc_off, const uint32_t* doc_len, const uint8_t* op, const int32_t* handle,
                           size_t n, int32_t* out_handles, int32_t* out_status, uint32_t* out_released, size_t* n_host) {
-    if (!e || !c || (n && (!doc_off || !doc_len || !op || !handle)) || (arena_len && !arena) || n > 0x7FFFFFF0ull)
+    if (!e || !c || (n && (!doc_off || !doc_len || !op || !handle)) || (arena_len && !arena) || n > 0x7FFFFFF0ull ||
+        arena_len > KWOK_JSON_ARENA_MAX)
         return KWOK_EINVAL;
     if (e->poisoned) return poisoned(e);
     drain(e);

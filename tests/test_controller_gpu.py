@@ -223,3 +223,57 @@ def shim_ingest_sequence(engine_cls, nodes):
     assert c == O["counters"] and c["pod_patch"] == 0 and c["heartbeat"] == NODES
     e.close()
     o.close()
+
+
+NINE_REQUIREMENTS = "tier in (custom),!s1,!s2,!s3,!s4,!s5,!s6,!s7,!s8"
+
+
+def nine_requirement_scenario(cs, c, ticks=4, nodes=10, per_tick=20):
+    """pods with and without tier=custom, created, modified, marked for deletion and deleted between ticks"""
+    for i in range(nodes):
+        cs.create(T.node("node-%03d" % i, managed=i % 5 != 4))
+    out, k = [], 0
+    for t in range(ticks):
+        for _ in range(per_tick):
+            lab = {"app": "web", "tier": "custom"} if k % 3 == 0 else {"app": "web"}
+            cs.create(T.pod("pod-%04d" % k, "node-%03d" % (k % nodes), status={"phase": "Pending"} if k % 4 else {},
+                            containers=(("c", "img:%d" % (k % 3)),), labels=lab))
+            k += 1
+        if t:
+            for j in range((t - 1) * per_tick, (t - 1) * per_tick + 6):
+                q = cs.get("pods", ("default", "pod-%04d" % j))
+                if j % 2:
+                    q["metadata"]["deletionTimestamp"] = "2024-01-01T00:00:10Z"
+                else:
+                    q["metadata"].setdefault("labels", {})["touched"] = "yes"
+                cs.update(q)
+            cs.delete("pods", ("default", "pod-%04d" % ((t - 1) * per_tick + 7)))
+        n0 = len(cs.calls)
+        c.step(T.S0 + 30 * (t + 1))
+        if cs.deliver == "queued":
+            cs.pump()
+        out.append(cs.calls[n0:])
+    return out
+
+
+@pytest.mark.parametrize("deliver", ["sync", "queued"])
+def test_selector_beyond_the_device_tables_engine_equals_oracle(deliver):
+    """a disregard selector of nine requirements does not fit the device's tables: every pod document of every
+    batch is completed by the host codec (json_complete), and the engine-backed controller with gpu_codec=True
+    still patches and deletes exactly what the oracle-backed controller does"""
+    kw = dict(manage_nodes_with_annotation_selector=T.MANAGE, cidr="10.0.0.1/24",
+              disregard_status_with_label_selector=NINE_REQUIREMENTS)
+    ce, co = FakeClientset(deliver=deliver), FakeClientset(deliver=deliver)
+    e = T.controller(ce, backend=Engine, **kw)  # (gpu_codec=True is the controller's default)
+    o = T.controller(co, backend=Oracle, **kw)
+    assert e.gpu_codec and not o.gpu_codec
+    a = nine_requirement_scenario(ce, e)
+    b = nine_requirement_scenario(co, o)
+    for t, (x, y) in enumerate(zip(a, b)):
+        assert x == y, "tick %d" % t
+    writes = [c for x in a for c in x]
+    assert len(writes) > 60 and any(c[0] == "delete" for c in writes) and any(c[0] != "delete" for c in writes), writes[:3]
+    assert e.stats.pod_docs_host > 80  # (every pod document went through the host completion)
+    assert ce.store == co.store
+    e.close()
+    o.close()
