@@ -493,6 +493,54 @@ enum {
 /* All zero while the directory is off. */
 int kwok_node_dir_stats(kwok_engine* e, uint64_t out[KWOK_NODE_DIR_STAT_COUNT]);
 
+/* ---- Patch responses ----------------------------------------------
+ *
+ * The response to one of the engine's own patches is the patched object itself,
+ *   {"kind":"Pod","metadata":{..},..}
+ * without a {"type":..,"object":..} envelope.  Bodies arrive with a known length and may
+ * hold newlines (?pretty), so the caller concatenates them and gives their spans: no
+ * line split.  The response framer gives one kwok_watch_frame per body; the notes of the
+ * echo ledger (kwok_response.h) and the re-entry of pods patched without a podIP are then
+ * taken from the resident bytes.
+ *
+ * Rules (the same on host and device, frame for frame):
+ *   - document i is buf[off[i], +dlen[i]); a span that does not lie inside [0, len):
+ *     KWOK_EINVAL for that frame only; len > 0xFFFFFFF0: KWOK_EINVAL for the call before
+ *     any byte is read;
+ *   - whitespace before and after the value is skipped (the apiserver's trailing \n); an
+ *     empty or all-whitespace span: KWOK_WATCH_NONE with status KWOK_OK;
+ *   - the value is one JSON object in the codec's grammar (depth <= 64 counted from the
+ *     body's root, the first occurrence of a key wins); anything else, or bytes behind
+ *     the value: KWOK_EINVAL;
+ *   - an OK frame: type KWOK_WATCH_MODIFIED, line_off = off[i], doc_off / doc_len the
+ *     object with its braces, the four metadata spans and KWOK_FRAME_ESC_* flags exactly
+ *     as the watch framer fills them for the same object.  Only the root's own `metadata`
+ *     is read (spec.template.metadata is not);
+ *   - an escape in a routed key (metadata, uid, resourceVersion, name, namespace) sends
+ *     the document to the host framer (*n_host). */
+/* Host framer.  frames[n].  Returns the number of frames whose status is not KWOK_OK, or
+ * KWOK_EINVAL. */
+int kwok_frame_responses(const char* buf, size_t len, const uint64_t* off, const uint32_t* dlen, size_t n,
+                         kwok_watch_frame* frames);
+/* GPU framer: uploads buf once, frames the documents there (k_resp_parse) and copies the
+ * frames back.  The buffer and its frames become THE resident stream under *stream_id
+ * (never 0), replacing whatever was resident, as kwok_frame_watch_gpu does: every framed
+ * entry that takes a stream_id then works on response frames unchanged (MODIFIED:
+ * KWOK_OP_UPSERT).  The caller's buffer must stay valid and unchanged until the next
+ * framing call or kwok_engine_destroy.  Return value as kwok_frame_responses; a failed
+ * call leaves no stream resident. */
+int kwok_frame_responses_gpu(kwok_engine* e, const char* buf, size_t len, const uint64_t* off, const uint32_t* dlen,
+                             size_t n, kwok_watch_frame* frames, size_t* n_host, uint64_t* stream_id);
+enum {
+    KWOK_RESP_STAT_FRAMES = 0,   /* frames framed by kwok_frame_responses_gpu */
+    KWOK_RESP_STAT_HOST_FRAMES,  /* ... of them decided by the host framer */
+    KWOK_RESP_STAT_BYTES,        /* buffer bytes uploaded */
+    KWOK_RESP_STAT_NOTE_CALLS,   /* note calls over response frames (kwok_response.h), past their checks */
+    KWOK_RESP_STAT_NOTES,        /* records they keyed as notes (stored ones count under KWOK_ECHO_STAT_NOTES too) */
+    KWOK_RESP_STAT_COUNT
+};
+int kwok_response_stats(kwok_engine* e, uint64_t out[KWOK_RESP_STAT_COUNT]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,7 @@ REFS_ANY_SLOT = 1   # KWOK_REFS_ANY_SLOT: kwok_refs_lookup answers what the slot
 REFS_HEARTBEAT, REFS_NODE_INIT, REFS_POD_PATCH, REFS_DELETE = range(4)  # KWOK_REFS_*: the tick's output lists
 REFS_STATS = ("binds", "notes", "unnamed", "reads", "not_found", "bytes")  # KWOK_REFS_STAT_* order
 NODE_DIR_STATS = ("lookups", "hits", "notes", "binds", "unbound", "bytes")  # KWOK_NODE_DIR_STAT_* order
+RESP_STATS = ("frames", "host_frames", "bytes", "note_calls", "notes")  # KWOK_RESP_STAT_* order (patch responses)
 
 
 class Ref(C.Structure):

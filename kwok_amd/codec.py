@@ -70,6 +70,22 @@ def frame_list(body, cap=None):
     return frames[:nf.value], info
 
 
+def frame_responses(buf, offs, lens):
+    """kwok_frame_responses, the host framer of patch response bodies (include/kwok_watch.h): document i =
+    buf[offs[i], +lens[i]) -> frames (WATCH_FRAME_DTYPE).  KwokError(EINVAL) for a buffer over 0xFFFFFFF0 bytes."""
+    import numpy as np
+    lib = load_engine_lib()
+    buf = bytes(buf)
+    off = np.ascontiguousarray(offs, np.uint64)
+    ln = np.ascontiguousarray(lens, np.uint32)
+    assert len(off) == len(ln)
+    frames = np.zeros(max(len(off), 1), abi.WATCH_FRAME_DTYPE)
+    rc = lib.kwok_frame_responses(buf or b"\0", len(buf), off.ctypes.data, ln.ctypes.data, len(off), frames.ctypes.data)
+    if rc < 0:
+        raise KwokError(rc, "frame_responses: %s" % lib.kwok_codec_last_error().decode())
+    return frames[:len(off)]
+
+
 def list_text(body, span, escaped=False):
     """the text of one of a ListInfo's string spans (decoded when its KWOK_LIST_ESC_* bit is set)"""
     raw = bytes(body[span.off:span.off + span.len])

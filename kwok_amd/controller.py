@@ -66,6 +66,12 @@ GPU (kwok_frame_watch_gpu), echoes are dropped by the frames' uid and
 resourceVersion, and the kept frames are ingested from the resident stream
 (kwok_ingest_nodes_framed / kwok_ingest_pods_framed, pods in the same runs): no
 object is decoded or serialised on the host.
+
+response_bytes=True (with the uid directory and the echo ledger) keeps step 5's
+responses bytes too: the clientset's patch_*_raw methods return each patch's response
+body, a tick's bodies are framed on the GPU (kwok_frame_responses_gpu), the echo notes
+are taken from the frames (kwok_echo_note_framed) and step 6's pods re-enter from the
+resident bytes (kwok_ingest_pods_framed_uid): DESIGN.md §27.
 """
 from __future__ import annotations
 
@@ -295,6 +301,9 @@ class Stats:
     bodies: int = 0
     echo_notes_refused: int = 0  # echo_ledger: notes the device ledger refused (a uid / version outside its domain)
     refs_missing: int = 0       # ref_directory: bodies not sent, their object has no name stored (never with typed / framed feeds)
+    responses_framed: int = 0   # response_bytes: response bodies framed on the device (one per successful patch)
+    responses_host: int = 0     # ... of them decoded on the host for any reason (an escaped routed key, uid or version)
+    response_bytes: int = 0     # ... their bytes, uploaded once
     rejected: list = field(default_factory=list)
 
 
@@ -311,7 +320,8 @@ class Controller:
                     max_pod_specs=4096)
 
     def __init__(self, conf: Config, backend=None, codec_threads=1, suppress_echoes=True, geometry=None,
-                 gpu_codec=True, uid_directory=False, echo_ledger=False, ref_directory=False, node_directory=False):
+                 gpu_codec=True, uid_directory=False, echo_ledger=False, ref_directory=False, node_directory=False,
+                 response_bytes=False):
         self.conf = conf
         # uid_directory: the engine's pod uid directory (kwok_watch.h) resolves metadata.uid -> handle on
         # the device; pod_by_uid stays empty (a uid the directory cannot key - empty, escaped in the
@@ -366,6 +376,18 @@ class Controller:
                 raise ValueError("node_directory needs the engine backend (kwok_node_dir_enable)")
             self.eng.node_dir_enable()
         self.hb_refs = []     # ref_directory: the heartbeat list's references of epoch hb_epoch
+        # response_bytes: the responses to the engine's own patches stay bytes (kwok_watch.h): the
+        # clientset is asked for raw bodies (patch_*_raw), a tick's bodies are framed on the device
+        # (kwok_frame_responses_gpu), the ledger's notes are taken from the frames (kwok_echo_note_framed) and
+        # the pods patched without a podIP re-enter from the resident bytes: no response is decoded here
+        self.resp = bool(response_bytes)
+        if self.resp:
+            if not (uid_directory and echo_ledger):
+                raise ValueError("response_bytes needs uid_directory=True and echo_ledger=True")
+            if not hasattr(self.eng, "frame_responses"):
+                raise ValueError("response_bytes needs the engine backend (kwok_frame_responses_gpu)")
+        self.rq = self._new_responses()
+        self.reentered_dev = 0  # response_bytes: pods that re-entered from the resident response bytes (step 6)
         self.codec = Codec(manage_all_nodes=conf.manage_all_nodes,
                            manage_nodes_with_annotation_selector=conf.manage_nodes_with_annotation_selector,
                            manage_nodes_with_label_selector=conf.manage_nodes_with_label_selector,
@@ -402,6 +424,12 @@ class Controller:
     def close(self):
         self.eng.close()
         self.codec.close()
+
+    @staticmethod
+    def _new_responses():
+        """response_bytes: the response bodies of one framing call, appended in apply order: the buffer, the
+        bodies' spans, and the indices of the pod patches without a podIP (they re-enter)"""
+        return {"buf": bytearray(), "off": [], "len": [], "re": []}
 
     # ---- Start: the watches (node_controller.go:119-143, pod_controller.go:130-153) ----
     def start(self):
@@ -490,10 +518,11 @@ class Controller:
         n = self._tick(now)
         # step 6: pods patched without a podIP re-enter at once (pod_controller.go:279-319)
         for _ in range(4):  # (a re-entered pod's second patch carries its IPs: one round suffices)
-            if not self.reenter:
+            if not self.reenter and not self.reentered_dev:
                 break
             objs, self.reenter = self.reenter, []
-            self.stats.reentered += len(objs)
+            self.stats.reentered += len(objs) + self.reentered_dev  # (response_bytes: ingested in _tick, from the bytes)
+            self.reentered_dev = 0
             ws = [WatchObj(o, _meta(o).get("uid", ""), _meta(o).get("resourceVersion", ""), False) for o in objs]
             self._flush_pods((ws, [json.dumps(w.obj, separators=(",", ":")).encode() for w in ws]))
             if self.conf.enable_cni:
@@ -1131,6 +1160,8 @@ class Controller:
         n += self._apply_patches(POD_PATCH, L["pp"], L["pp_off"], L["pp_len"], abi.REFS_POD_PATCH)
         gone = []
         dl_refs = self._read_refs(abi.REFS_DELETE, 0, res.n_delete) if self.refs else None  # (the tick freed them: their bytes stay)
+        if self.resp:  # call 1: the heartbeat, node-init and pod-patch responses, in apply order (every list is read)
+            self._flush_responses()
         for k, (h, f) in enumerate(zip(L["dl"], L["dlf"])):  # Patch(removeFinalizers) if finalizers, then Delete(grace 0)
             # the engine freed the handle: the pod's noted echoes go BEFORE the apply, so
             # that the echo of its finalizer patch (noted by the apply) is dropped
@@ -1145,8 +1176,62 @@ class Controller:
             self.pod_by_uid.pop(uid, None)
             self.pod_ref.pop(h, None)
         self.stats.bodies += n
-        self._send_echo()
+        self._send_echo()  # (response_bytes: call 2, the delete list's forgets - behind call 1's notes)
+        if self.resp:      # call 3: the finalizer-patch responses.  A uid is in one delete list once: the per-uid
+            self._flush_responses()  # order of the three calls is the interleaved order of the queue
+            self._send_echo()  # (the notes of responses whose uid / version holds an escape: decoded here)
         return n
+
+    def _response(self, raw, reenter=False):
+        """response_bytes: one response body joins the tick's buffer"""
+        q = self.rq
+        q["off"].append(len(q["buf"]))
+        q["len"].append(len(raw))
+        q["buf"] += raw
+        if reenter:
+            q["re"].append(len(q["off"]) - 1)
+
+    def _flush_responses(self):
+        """response_bytes: the collected bodies framed on the device, one note per response from its frame, and
+        the pod patches without a podIP ingested from the resident bytes by uid (not the echo entry: like the
+        host path's re-entry it is not dropped as its own echo; the note stays for the watch echo).  Fallbacks as
+        _ingest_frames_ledger's: a response whose uid / resourceVersion holds an escape is decoded here and its
+        text noted through kwok_echo_update; a re-entering one with an escaped uid takes the document path."""
+        q, self.rq = self.rq, self._new_responses()
+        n = len(q["off"])
+        if not n:
+            return
+        buf = bytes(q["buf"])
+        frames, n_host, sid = self.eng.frame_responses(buf, q["off"], q["len"])
+        self.stats.responses_framed += n
+        self.stats.response_bytes += len(buf)
+        body = lambda i: buf[q["off"][i]:q["off"][i] + q["len"][i]]  # noqa: E731
+        st = self.eng.echo_note_framed(sid, np.arange(n, dtype=np.uint32))
+        fl = frames["flags"]
+        host = set()
+        esc = np.nonzero((st == abi.EDOMAIN) & ((fl & (abi.FRAME_ESC_UID | abi.FRAME_ESC_RV)) != 0))[0].tolist()
+        for i in esc:
+            md = _meta(json.loads(body(i)))
+            self._note(md.get("uid"), md.get("resourceVersion"))
+            host.add(i)
+        self.stats.echo_notes_refused += int((st != abi.OK).sum()) - len(esc)
+        if q["re"]:
+            idx = np.array(q["re"], np.uint32)
+            _hs, s2, _rel, nh, runs = self.eng.ingest_pods_framed_uid(self.codec, sid, idx)
+            self.stats.pod_records += len(idx)
+            self.stats.pod_runs += runs
+            self.stats.pod_docs_host += nh
+            for k, i in enumerate(idx.tolist()):
+                if s2[k] == abi.EDOMAIN and fl[i] & abi.FRAME_ESC_UID:
+                    self.reenter.append(json.loads(body(i)))  # (step 6 sends it through the document path)
+                    host.add(i)
+                    continue
+                self.reentered_dev += 1
+                if s2[k] not in (abi.OK, NOT_SENT):
+                    f = frames[i]
+                    self.stats.rejected.append(("pod", buf[int(f["name"]["off"]):int(f["name"]["off"]) + int(f["name"]["len"])]
+                                                .decode(errors="replace"), int(s2[k])))
+        self.stats.responses_host += n_host + len(host)
 
     REFS_PIECE = 1 << 16  # ref_directory: references read per kwok_read_refs call at most
 
@@ -1180,16 +1265,21 @@ class Controller:
             return
         if kind in (HEARTBEAT, NODE_INIT):  # configureHeartbeatNode / configureNode bodies
             try:
-                obj = cs.patch_node_status(ref[2].decode() if ref else self.node_name[h], body)
+                obj = (cs.patch_node_status_raw if self.resp else cs.patch_node_status)(
+                    ref[2].decode() if ref else self.node_name[h], body)
             except NotFound:
                 return
+            if self.resp:
+                return self._response(obj)
             self._note(_meta(obj).get("uid"), _meta(obj).get("resourceVersion"))
         elif kind == POD_PATCH:  # LockPod (pod_controller.go:205-231)
             ns, name = (ref[1].decode(), ref[2].decode()) if ref else self.pod_ref[h]
             try:
-                obj = cs.patch_pod_status(ns, name, body)
+                obj = (cs.patch_pod_status_raw if self.resp else cs.patch_pod_status)(ns, name, body)
             except NotFound:
                 return
+            if self.resp:  # (an empty status: its frame re-enters from the resident bytes)
+                return self._response(obj, b'"podIP"' not in body)
             self._note(_meta(obj).get("uid"), _meta(obj).get("resourceVersion"))
             if b'"podIP"' not in body:  # an empty status: its echo re-enters (step 6)
                 self.reenter.append(obj)
@@ -1200,10 +1290,13 @@ class Controller:
                     from .engine import finalizer_patch
                     self.finalizer = finalizer_patch()
                 try:
-                    obj = cs.patch_pod(ns, name, self.finalizer)
+                    obj = (cs.patch_pod_raw if self.resp else cs.patch_pod)(ns, name, self.finalizer)
                 except NotFound:
                     return
-                self._note(_meta(obj).get("uid"), _meta(obj).get("resourceVersion"))
+                if self.resp:
+                    self._response(obj)
+                else:
+                    self._note(_meta(obj).get("uid"), _meta(obj).get("resourceVersion"))
             try:
                 cs.delete_pod(ns, name)
             except NotFound:

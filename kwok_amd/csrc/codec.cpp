@@ -983,6 +983,46 @@ bool kwok::frame_item(const char* body, uint32_t lo, uint32_t hi, kwok_watch_fra
     return true;
 }
 
+// ---------------------------------------------------------------- response frames
+// kwok_frame_responses (kwok_watch.h): the host framer of patch response bodies, the
+// yardstick of the device framer (json.hip k_resp_parse) and the decider of what that
+// one lists.  A body is the patched object itself (client-go: Patch(...).Do(ctx).Raw());
+// its frame is the one the watch framer gives the same object in a MODIFIED envelope.
+void kwok::frame_response(const char* buf, uint32_t lo, uint32_t hi, kwok_watch_frame* f) {
+    memset(f, 0, sizeof *f);
+    f->line_off = lo;
+    f->type = KWOK_WATCH_NONE;
+    f->status = KWOK_OK;
+    uint32_t k = lo;
+    while (k < hi && (buf[k] == ' ' || buf[k] == '\t' || buf[k] == '\r' || buf[k] == '\n')) k++;
+    if (k == hi) return;  // an empty body
+    f->status = KWOK_EINVAL;
+    std::deque<std::string> store;
+    JV root;
+    Parser ps(buf, lo, hi - lo, &store);
+    if (!ps.document(root) || root.t != JV::OBJ) return;
+    item_frame(root, f);
+    f->type = KWOK_WATCH_MODIFIED;
+    f->line_off = lo;
+}
+
+extern "C" int kwok_frame_responses(const char* buf, size_t len, const uint64_t* off, const uint32_t* dlen, size_t n,
+                                    kwok_watch_frame* frames) {
+    if (len > 0xFFFFFFF0ull || (len && !buf) || (n && (!off || !dlen || !frames)))
+        return fail(KWOK_EINVAL, "kwok_frame_responses: null argument or buffer > 4 GiB");
+    int bad = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (off[i] > len || dlen[i] > len - off[i]) {  // a span outside the buffer: no byte is read
+            memset(&frames[i], 0, sizeof frames[i]);
+            frames[i].status = KWOK_EINVAL;
+        } else {
+            kwok::frame_response(buf, (uint32_t)off[i], (uint32_t)(off[i] + dlen[i]), &frames[i]);
+        }
+        bad += frames[i].status != KWOK_OK;
+    }
+    return bad;
+}
+
 int kwok::list_envelope(const char* body, size_t len, uint32_t open, uint32_t close, kwok_list_info* info) {
     if (open >= close || close >= len) return KWOK_EINVAL;
     std::string env(body, (size_t)open + 1);

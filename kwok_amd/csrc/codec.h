@@ -12,6 +12,8 @@ void frame_line(const char* stream, uint32_t lo, uint32_t hi, kwok_watch_frame* 
 // the host framer over one item [lo, hi) of a List body (kwok_watch.h): false when the
 // span is not one JSON object at the items' depth that fills it
 bool frame_item(const char* body, uint32_t lo, uint32_t hi, kwok_watch_frame* f);
+// the host framer over one response body [lo, hi) (kwok_watch.h): the object at the root
+void frame_response(const char* buf, uint32_t lo, uint32_t hi, kwok_watch_frame* f);
 // the envelope of a List body whose root holds one array [open, close] (the
 // brackets' offsets): the body with that array emptied is parsed.  KWOK_EINVAL: it
 // is no JSON object; 1: it is, but its first `items` is not that array (info

@@ -35,7 +35,7 @@ struct EchoCall {  // per call, reset by the host, read back once
     uint32_t n_bad;      // update: ops whose status is not KWOK_OK
     uint32_t err;        // the scratch tables wrapped or ran over
     uint32_t n_new;      // update: uids with a note and no entry that holds one (each may take a pool entry)
-    uint32_t pad;
+    uint32_t n_note;     // note_framed: records keyed as notes
 };
 
 // tab: [mask + 1] pool index + 1 (0: empty) at the low bits of the uid's hash, linear probing
@@ -97,6 +97,8 @@ struct EchoKeep {
 void launch_echo_key_update(const EchoBatch& B, const EchoSpans& P, int32_t* status, hipStream_t st);
 void launch_echo_key_typed(const EchoBatch& B, const EchoSpans& P, hipStream_t st);
 void launch_echo_key_frames(const EchoBatch& B, const EchoFrames& F, hipStream_t st);
+// k_echo_key_note_frames: every ingestible frame a note of its (uid, rv); status[i] as kwok_echo_note_framed states it
+void launch_echo_key_note_frames(const EchoBatch& B, const EchoFrames& F, int32_t* status, hipStream_t st);
 // k_echo_claim, k_echo_group, k_echo_alloc, k_echo_scatter
 void launch_echo_group(const EchoBatch& B, hipStream_t st);
 // k_echo_need: the call's n_new, before anything is stored

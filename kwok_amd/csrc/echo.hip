@@ -177,6 +177,40 @@ __global__ __launch_bounds__(256) void k_echo_key_frames(EchoBatch B, EchoFrames
     key_store(B, i, kind, uoff, ulen, roff, rlen);
     B.res[i] = res;
 }
+// k_echo_key_frames for notes (kwok_echo_note_framed): every ingestible frame is a note of its (uid, rv),
+// under k_echo_key_update's rules for a KWOK_ECHO_NOTE with the same pair
+__global__ __launch_bounds__(256) void k_echo_key_note_frames(EchoBatch B, EchoFrames F, int32_t* status) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool bad = false, note = false;
+    if (i < B.n) {
+        const uint32_t fi = F.frame_idx[i];
+        int32_t s = KWOK_EINVAL;
+        uint8_t kind = EK_SKIP;
+        uint32_t uoff = 0, ulen = 0, roff = 0, rlen = 0;
+        if (fi < F.n_frames) {
+            const kwok_watch_frame f = F.frames[fi];
+            if (f.status == KWOK_OK && (f.type == KWOK_WATCH_ADDED || f.type == KWOK_WATCH_MODIFIED || f.type == KWOK_WATCH_DELETED)) {
+                const kwok_str u = f.uid, r = f.resource_version;
+                if ((f.flags & (KWOK_FRAME_ESC_UID | KWOK_FRAME_ESC_RV)) || u.len > KWOK_UID_MAX || r.len > KWOK_RV_MAX) {
+                    s = KWOK_EDOMAIN;
+                } else if (!u.len || !r.len) {
+                    s = KWOK_OK;  // ignored
+                } else if (span_ok(u.off, u.len, B.base_len) && span_ok(r.off, r.len, B.base_len)) {
+                    s = KWOK_OK;
+                    kind = EK_NOTE;
+                    uoff = u.off, ulen = u.len, roff = r.off, rlen = r.len;
+                }
+            }
+        }
+        key_store(B, i, kind, uoff, ulen, roff, rlen);
+        B.res[i] = 0;
+        status[i] = s;
+        bad = s != KWOK_OK;
+        note = kind == EK_NOTE;
+    }
+    wave_sum32(bad, &B.call->n_bad);
+    wave_sum32(note, &B.call->n_note);
+}
 
 // ---- grouping by uid ----
 __device__ __forceinline__ bool same_uid(const EchoBatch& B, uint32_t a, const uint8_t* key, uint32_t len) {
@@ -518,6 +552,9 @@ void launch_echo_key_typed(const EchoBatch& B, const EchoSpans& P, hipStream_t s
 }
 void launch_echo_key_frames(const EchoBatch& B, const EchoFrames& F, hipStream_t st) {
     if (B.n) hipLaunchKernelGGL(k_echo_key_frames, dim3(cdiv(B.n, 256)), dim3(256), 0, st, B, F);
+}
+void launch_echo_key_note_frames(const EchoBatch& B, const EchoFrames& F, int32_t* status, hipStream_t st) {
+    if (B.n) hipLaunchKernelGGL(k_echo_key_note_frames, dim3(cdiv(B.n, 256)), dim3(256), 0, st, B, F, status);
 }
 void launch_echo_group(const EchoBatch& B, hipStream_t st) {
     if (!B.n) return;

@@ -13,6 +13,7 @@
 //
 // The tick queue (output slots and arena, enqueue / retire, submit / collect) is engine_tick.cpp;
 // engine_state.h holds the state both files work on.
+#include "../../include/kwok_response.h"
 #include "engine_state.h"
 #include "node_spans.h"
 
@@ -2451,6 +2452,83 @@ int kwok_watch_stats(kwok_engine* e, uint64_t out[KWOK_WATCH_STAT_COUNT]) {
     return KWOK_OK;
 }
 
+// ---- patch responses (kwok_watch.h): the caller's spans, one thread per document; the
+// buffer and its frames become the resident stream, as a watch stream does ----
+int kwok_frame_responses_gpu(kwok_engine* e, const char* buf, size_t len, const uint64_t* off, const uint32_t* dlen,
+                             size_t n, kwok_watch_frame* frames, size_t* n_host, uint64_t* stream_id) {
+    if (n_host) *n_host = 0;
+    if (stream_id) *stream_id = 0;
+    if (!e || !stream_id || len > 0xFFFFFFF0ull || (len && !buf) || (n && (!off || !dlen || !frames)) || n > 0x7FFFFFF0ull)
+        return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    auto& Wt = e->watch;
+    hipStream_t st = e->st;
+    Wt.id = 0;  // (a failed call leaves no stream resident)
+    Wt.frames_h.clear();
+    int rc = watch_reserve(e, len);
+    if (rc) return rc;
+    const size_t padded = ((len + 15) & ~(size_t)15) + 16;
+    const auto t0 = clk::now();
+    ProfEvents<2> pe(e->iprof, e->st);
+    if (len) HIPCHK(e, hipMemcpyAsync(Wt.stream, buf, len, hipMemcpyHostToDevice, st));
+    HIPCHK(e, hipMemsetAsync(Wt.stream + len, 0, padded - len, st));
+    Wt.rstats[KWOK_RESP_STAT_BYTES] += len;
+    uint32_t nh = 0;
+    int bad = 0;
+    if (n) {
+        if ((rc = Wt.lines.reserve(e, n)) || (rc = Wt.rspans.reserve(e, n))) return rc;
+        HIPCHK(e, hipMemcpyAsync(Wt.r_off, off, n * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipMemcpyAsync(Wt.r_len, dlen, n * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(e, hipMemsetAsync(Wt.counts + 1, 0, 4, st));
+        pe.stamp(0);
+        launch_resp_parse(Wt.stream, len, Wt.r_off, Wt.r_len, (uint32_t)n, Wt.frames, Wt.host_list, Wt.counts + 1, st);
+        HIPCHK(e, hipGetLastError());
+        pe.stamp(1);
+        Wt.frames_h.resize(n);
+        HIPCHK(e, hipMemcpyAsync(Wt.frames_h.data(), Wt.frames, n * sizeof(kwok_watch_frame), hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipMemcpyAsync(Wt.counts_h + 1, Wt.counts + 1, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(e, hipStreamSynchronize(st));
+        nh = Wt.counts_h[1];
+        if (nh > n) {
+            Wt.frames_h.clear();
+            return e->fail(KWOK_EDEVICE, "response framer: %u of %zu documents listed", nh, n);
+        }
+        if (nh) {  // the documents the device listed: the host framer over the caller's bytes
+            std::vector<uint32_t> list(nh);
+            HIPCHK(e, hipMemcpyAsync(list.data(), Wt.host_list, (size_t)nh * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(e, hipStreamSynchronize(st));
+            for (uint32_t i : list) {
+                if (i >= n || off[i] > len || dlen[i] > len - off[i]) {
+                    Wt.frames_h.clear();
+                    return e->fail(KWOK_EDEVICE, "response framer: listed document %u of %zu", i, n);
+                }
+                frame_response(buf, (uint32_t)off[i], (uint32_t)(off[i] + dlen[i]), &Wt.frames_h[i]);
+                HIPCHK(e, hipMemcpyAsync(Wt.frames + i, &Wt.frames_h[i], sizeof(kwok_watch_frame), hipMemcpyHostToDevice, st));
+            }
+            HIPCHK(e, hipStreamSynchronize(st));
+        }
+        for (size_t i = 0; i < n; i++) bad += Wt.frames_h[i].status != KWOK_OK;
+        memcpy(frames, Wt.frames_h.data(), n * sizeof(kwok_watch_frame));
+    } else {
+        HIPCHK(e, hipStreamSynchronize(st));
+    }
+    if (n_host) *n_host = nh;
+    Wt.len = len, Wt.host = buf;
+    Wt.rstats[KWOK_RESP_STAT_FRAMES] += n;
+    Wt.rstats[KWOK_RESP_STAT_HOST_FRAMES] += nh;
+    *stream_id = Wt.id = Wt.next_id++;
+    if (pe.on())
+        fprintf(stderr, "[kwok responses] %zu bytes, %zu documents (%u by the host): k_resp_parse %.3f ms; the call %.2f ms\n",
+                len, n, nh, n ? pe.elapsed(0, 1) : 0.f, ms_between(t0, clk::now()));
+    return bad;
+}
+
+int kwok_response_stats(kwok_engine* e, uint64_t out[KWOK_RESP_STAT_COUNT]) {
+    if (!e || !out) return KWOK_EINVAL;
+    for (int k = 0; k < KWOK_RESP_STAT_COUNT; k++) out[k] = e->watch.rstats[k];
+    return KWOK_OK;
+}
+
 // ---- List bodies (kwok_watch.h): split by bracket depth on the device, the items
 // parsed there, the envelope by the host from the caller's bytes ----
 namespace {
@@ -3318,6 +3396,36 @@ int kwok_echo_update(kwok_engine* e, const uint8_t* op, const char* arena, const
     HIPCHK(e, hipGetLastError());
     if (out_status) HIPCHK(e, hipMemcpyAsync(out_status, E.s_status, n * 4, hipMemcpyDeviceToHost, st));
     if ((rc = echo_read(e, true))) return rc;
+    return (int)E.call_h->n_bad;
+}
+
+// kwok_echo_update's notes with the pairs read from the resident frames (kwok_response.h): only the keying
+// front end differs, the grouping, the room check and the apply are kwok_echo_update's
+int kwok_echo_note_framed(kwok_engine* e, uint64_t stream_id, const uint32_t* frame_idx, size_t n, int32_t* out_status) {
+    if (!e || (n && !frame_idx) || n > 0x7FFFFFF0ull) return KWOK_EINVAL;
+    int rc = echo_enter(e, "kwok_echo_note_framed");
+    if (rc) return rc;
+    if ((rc = stream_resident(e, stream_id))) return rc;
+    auto& E = e->echo;
+    auto& Wt = e->watch;
+    Wt.rstats[KWOK_RESP_STAT_NOTE_CALLS]++;
+    if (!n) return 0;
+    if ((rc = echo_reserve(e, n))) return rc;
+    hipStream_t st = e->st;
+    HIPCHK(e, hipMemcpyAsync(E.fidx, frame_idx, n * 4, hipMemcpyHostToDevice, st));
+    const EchoBatch B = echo_batch(e, Wt.stream, Wt.len, n);
+    const EchoFrames F{Wt.frames, (uint32_t)Wt.frames_h.size(), E.fidx};
+    launch_echo_key_note_frames(B, F, E.res_st, st);
+    launch_echo_group(B, st);
+    launch_echo_need(E.ledger(), B, st);
+    HIPCHK(e, hipGetLastError());
+    // the room the call needs, before anything is stored: compacted, grown or refused here
+    if ((rc = echo_read(e, true)) || (rc = echo_ensure(e, E.call_h->n_new))) return rc;
+    launch_echo_update(E.ledger(), B, st);
+    HIPCHK(e, hipGetLastError());
+    if (out_status) HIPCHK(e, hipMemcpyAsync(out_status, E.res_st, n * 4, hipMemcpyDeviceToHost, st));
+    if ((rc = echo_read(e, true))) return rc;
+    Wt.rstats[KWOK_RESP_STAT_NOTES] += E.call_h->n_note;
     return (int)E.call_h->n_bad;
 }
 

@@ -237,6 +237,12 @@ struct kwok_engine {
         DevArr<uint32_t> lc;           // [KWOK_LIST_COUNTERS]
         Pinned<uint32_t> lc_h;         // [KWOK_LIST_COUNTERS]
         uint64_t lstats[KWOK_LIST_STAT_COUNT] = {};
+        // the response framer (json.hip k_resp_parse): the documents' spans (nothing is
+        // allocated before the first kwok_frame_responses_gpu)
+        DevArr<uint64_t> r_off;        // [rspans.cap]
+        DevArr<uint32_t> r_len;        // [rspans.cap]
+        DevGroup rspans{4096, {r_off, r_len}};
+        uint64_t rstats[KWOK_RESP_STAT_COUNT] = {};
     } watch;
 
     // ---- relist with Replace (resync.hip, kwok_watch.h): a `seen` byte per slot of each

@@ -1431,7 +1431,10 @@ __device__ __forceinline__ uint32_t wave_incl(uint32_t v, uint32_t lane) {
 }
 
 enum : uint8_t { F_NONE = 0, F_TYPE, F_OBJ, F_META, F_UID, F_RV, F_NAME, F_NS };
-struct FrameScan {
+// S: how far the routed depths are shifted up.  0: a watch line, the object under the root's
+// `object`; 1: a response body (k_resp_parse), the object IS the root - no `type` / `object` keys
+template <int S>
+struct FrameScanT {
     JRd* r;
     uint8_t next = F_NONE;
     bool err = false, host = false, root_obj = false;
@@ -1449,16 +1452,16 @@ struct FrameScan {
     }
     __device__ void key(int d, const JTok& t) {
         next = F_NONE;
-        const bool routed = d == 0 || (d == 1 && in_obj) || (d == 2 && in_meta);
+        const bool routed = (!S && d == 0) || (d == 1 - S && in_obj) || (d == 2 - S && in_meta);
         if (!routed) return;
         if (t.esc) {  // a routed key is compared as decoded text: the host framer decides the line
             host = true;
             return;
         }
-        if (d == 0) {
+        if (!S && d == 0) {
             if (lit_eq(*r, t.off, t.len, "type")) next = first(seen_root, 0, F_TYPE);
             else if (lit_eq(*r, t.off, t.len, "object")) next = first(seen_root, 1, F_OBJ);
-        } else if (d == 1) {
+        } else if (d == 1 - S) {
             if (lit_eq(*r, t.off, t.len, "metadata")) next = first(seen_obj, 0, F_META);
         } else {
             if (lit_eq(*r, t.off, t.len, "uid")) next = first(seen_meta, 0, F_UID);
@@ -1469,7 +1472,7 @@ struct FrameScan {
     }
     __device__ void scalar(int d, const JTok& t, bool pa) {
         if (pa || d == 0) return;
-        if (d == 1) {
+        if (!S && d == 1) {
             if (next == F_OBJ) err = true;  // object must be a JSON object
             if (next != F_TYPE) return;
             if (t.kind != J_STR) err = true;
@@ -1482,7 +1485,7 @@ struct FrameScan {
             else err = true;  // "got invalid watch event type"
             return;
         }
-        if (d != 3 || !in_meta || t.kind != J_STR) return;  // (a non-string value: an empty span)
+        if (d != 3 - S || !in_meta || t.kind != J_STR) return;  // (a non-string value: an empty span)
         const Span s = t.len ? Span{(uint32_t)t.off, t.len} : Span{0, 0};
         switch (next) {
             case F_UID: uid = s; if (t.esc) flags |= KWOK_FRAME_ESC_UID; break;
@@ -1495,23 +1498,25 @@ struct FrameScan {
     __device__ void begin(int d, bool a, bool pa) {
         if (d == 0) {
             root_obj = !a;
+            if (S && !a) in_obj = obj_set = true, obj_pos = r->pos - 1;
             return;
         }
         if (pa) return;
-        if (d == 1) {
+        if (!S && d == 1) {
             if (next == F_TYPE) err = true;  // type must be a string
             if (next != F_OBJ) return;
             if (a) err = true;
             else in_obj = obj_set = true, obj_pos = r->pos - 1;
-        } else if (d == 2 && in_obj && next == F_META && !a) {
+        } else if (d == 2 - S && in_obj && next == F_META && !a) {
             in_meta = true;
         }
     }
     __device__ void end(int d, bool, bool) {
-        if (d == 1 && in_obj) in_obj = false, obj_len = (uint32_t)(r->pos - obj_pos);
-        if (d == 2) in_meta = false;
+        if (d == 1 - S && in_obj) in_obj = false, obj_len = (uint32_t)(r->pos - obj_pos);
+        if (d == 2 - S) in_meta = false;
     }
 };
+using FrameScan = FrameScanT<0>;
 }  // namespace
 
 __global__ __launch_bounds__(FR_THREADS) void k_frame_count(const uint8_t* s, uint64_t len, uint32_t* tile_cnt) {
@@ -1628,6 +1633,52 @@ __global__ __launch_bounds__(256) void k_frame_parse(const uint8_t* s, const uin
     frames[i] = f;
 }
 
+// the response framer (kwok_watch.h, kwok_frame_responses_gpu): one thread per document
+// [off[i], +dlen[i]) of the uploaded buffer, the object at the root (FrameScanT<1>); a span
+// that does not lie inside the buffer is refused before a byte of it is read
+__global__ __launch_bounds__(256) void k_resp_parse(const uint8_t* s, uint64_t len, const uint64_t* off, const uint32_t* dlen,
+                                                    uint32_t n, kwok_watch_frame* frames, uint32_t* host_list, uint32_t* n_host) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t o = off[i];
+    const uint32_t l = dlen[i];
+    kwok_watch_frame f;
+    f.line_off = f.doc_off = f.doc_len = 0;
+    f.type = KWOK_WATCH_NONE, f.flags = 0, f.status = KWOK_OK, f.reserved0 = 0;
+    f.uid = f.resource_version = f.name = f.namespace_ = kwok_str{0, 0};
+    if (o > len || l > len - o) {
+        f.status = KWOK_EINVAL;
+        frames[i] = f;
+        return;
+    }
+    const jpos lo = (jpos)o, hi = lo + l;
+    f.line_off = lo;
+    JRd rd{s, lo, hi, ~0u, make_uint4(0, 0, 0, 0)};
+    for (;;) {  // a span of only whitespace: KWOK_WATCH_NONE
+        const int c = rd.peek();
+        if (c != ' ' && c != '\t' && c != '\n' && c != '\r') break;
+        rd.pos++;
+    }
+    if (rd.pos < hi) {
+        FrameScanT<1> p;
+        p.r = &rd;
+        const bool ok = jparse(rd, p);  // (d0 = 0: only whitespace may follow the value)
+        if (!ok || !p.root_obj) {
+            f.status = KWOK_EINVAL;
+        } else if (p.host) {
+            host_list[atomicAdd(n_host, 1u)] = i;  // (its frame is the host framer's)
+        } else {
+            f.type = KWOK_WATCH_MODIFIED, f.flags = p.flags;
+            f.doc_off = p.obj_pos, f.doc_len = p.obj_len;
+            f.uid = kwok_str{p.uid.off, p.uid.len};
+            f.resource_version = kwok_str{p.rv.off, p.rv.len};
+            f.name = kwok_str{p.name.off, p.name.len};
+            f.namespace_ = kwok_str{p.ns.off, p.ns.len};
+        }
+    }
+    frames[i] = f;
+}
+
 void launch_frame_count(const uint8_t* s, uint64_t len, uint32_t n_tiles, uint32_t* tile_cnt, hipStream_t st) {
     if (n_tiles) hipLaunchKernelGGL(k_frame_count, dim3(n_tiles), dim3(FR_THREADS), 0, st, s, len, tile_cnt);
 }
@@ -1644,6 +1695,12 @@ void launch_frame_parse(const uint8_t* s, const uint32_t* ends, uint32_t n, kwok
     if (!n) return;
     const uint32_t bs = json_block(n);
     hipLaunchKernelGGL(k_frame_parse, dim3((n + bs - 1) / bs), dim3(bs), 0, st, s, ends, n, frames, host_list, n_host);
+}
+void launch_resp_parse(const uint8_t* s, uint64_t len, const uint64_t* off, const uint32_t* dlen, uint32_t n,
+                       kwok_watch_frame* frames, uint32_t* host_list, uint32_t* n_host, hipStream_t st) {
+    if (!n) return;
+    const uint32_t bs = json_block(n);
+    hipLaunchKernelGGL(k_resp_parse, dim3((n + bs - 1) / bs), dim3(bs), 0, st, s, len, off, dlen, n, frames, host_list, n_host);
 }
 
 // ---------------------------------------------------------------------------

@@ -308,6 +308,9 @@ void launch_frame_emit(const uint8_t* s, uint64_t len, uint32_t n_tiles, const u
 // one thread per line: frames[i], or i listed for the host framer (*n_host zeroed by the caller)
 void launch_frame_parse(const uint8_t* s, const uint32_t* ends, uint32_t n, kwok_watch_frame* frames, uint32_t* host_list,
                         uint32_t* n_host, hipStream_t st);
+// the response framer: one thread per document [off[i], +dlen[i]) of s, the object at the root (k_resp_parse)
+void launch_resp_parse(const uint8_t* s, uint64_t len, const uint64_t* off, const uint32_t* dlen, uint32_t n,
+                       kwok_watch_frame* frames, uint32_t* host_list, uint32_t* n_host, hipStream_t st);
 
 // ---- the List body framer (json.hip, kwok_watch.h): the same buffer and tiles ----
 enum : uint32_t {  // the framer's device counters lc[KWOK_LIST_COUNTERS], read back by engine.cpp

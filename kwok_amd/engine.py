@@ -145,6 +145,10 @@ def declare(lib, pre):
             "node_lookup": (C.c_int, [VP, VP, VP, VP, SZ, VP]),
             "node_bind": (C.c_int, [VP, VP, VP, VP, VP, SZ, P(SZ)]),
             "node_dir_stats": (C.c_int, [VP, VP]),
+            "frame_responses": (C.c_int, [VP, SZ, VP, VP, SZ, VP]),
+            "frame_responses_gpu": (C.c_int, [VP, VP, SZ, VP, VP, SZ, VP, P(SZ), P(U64)]),
+            "echo_note_framed": (C.c_int, [VP, U64, VP, SZ, VP]),
+            "response_stats": (C.c_int, [VP, VP]),
         })
     for name, (res, args) in sig.items():
         f = getattr(lib, pre + name, None)
@@ -852,6 +856,41 @@ class Engine(EngineBase):
         out = (C.c_uint64 * len(abi.ECHO_STATS))()
         self._check(self._lib.kwok_echo_stats(self._h, out), "echo_stats")
         return dict(zip(abi.ECHO_STATS, list(out)))
+
+    # ---- patch responses (include/kwok_watch.h, kwok_response.h): framed on the GPU, noted from the frames ----
+    def frame_responses(self, buf, offs, lens):
+        """kwok_frame_responses_gpu over the concatenated response bodies of the engine's own patches, document i
+        = buf[offs[i], +lens[i]): (frames (WATCH_FRAME_DTYPE, OK frames MODIFIED), documents the host framed,
+        stream_id).  The buffer stays resident as the stream for echo_note_framed and every framed ingest until
+        the next framing call; the engine keeps a reference to the bytes."""
+        data = np.frombuffer(buf, np.uint8) if len(buf) else np.zeros(1, np.uint8)
+        off = np.ascontiguousarray(offs, np.uint64)
+        ln = np.ascontiguousarray(lens, np.uint32)
+        assert len(off) == len(ln)
+        n = len(off)
+        frames = np.zeros(max(n, 1), abi.WATCH_FRAME_DTYPE)
+        nh, sid = C.c_size_t(), C.c_uint64()
+        self._watch_buf = None
+        rc = self._lib.kwok_frame_responses_gpu(self._h, data.ctypes.data, len(buf), off.ctypes.data, ln.ctypes.data, n,
+                                                frames.ctypes.data, C.byref(nh), C.byref(sid))
+        self._check(rc, "frame_responses_gpu")
+        self._watch_buf = data
+        return frames[:n], nh.value, sid.value
+
+    def echo_note_framed(self, stream_id, frame_idx):
+        """kwok_echo_note_framed: one note per record, (uid, resourceVersion) read from frame frame_idx[i] of the
+        resident stream, in array order per uid -> the per-record statuses"""
+        idx = np.ascontiguousarray(frame_idx, np.uint32)
+        st = np.empty(len(idx), np.int32)
+        rc = self._lib.kwok_echo_note_framed(self._h, stream_id, idx.ctypes.data, len(idx), st.ctypes.data)
+        self._check(rc, "echo_note_framed")
+        return st
+
+    def response_stats(self):
+        """kwok_response_stats: frames framed / of them by the host / bytes uploaded / note calls / notes keyed"""
+        out = (C.c_uint64 * len(abi.RESP_STATS))()
+        self._check(self._lib.kwok_response_stats(self._h, out), "response_stats")
+        return dict(zip(abi.RESP_STATS, list(out)))
 
     # ---- the pod and node reference directory (include/kwok_watch.h): what a patch is addressed to ----
     def refs_enable(self):
