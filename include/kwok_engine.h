@@ -647,6 +647,12 @@ int kwok_ingest_pods_json(kwok_engine* e, const kwok_codec* c, const char* arena
 int kwok_ingest_nodes_json(kwok_engine* e, const kwok_codec* c, const char* arena, size_t arena_len,
                            const uint64_t* doc_off, const uint32_t* doc_len, const uint8_t* op, size_t n,
                            int32_t* out_handles, int32_t* out_status, size_t* n_host);
+/* The status blob canonicaliser (kwok_canon.h, off by default): with kwok_canon_enable
+ * the device writes the canonical addresses / allocatable / capacity itself for every
+ * document whose blobs are inside its domain, into a buffer of its own; such a document
+ * is decoded with no host codec call and is not counted in *n_host.  Every output of
+ * this entry, of kwok_decode_nodes_gpu and of the framed node ingests stays byte for
+ * byte what it is without it. */
 /* kwok_decode_nodes_gpu: the decode alone (tests, diagnostics): per document
  * the kwok_node_event kwok_decode_node writes (op UPSERT) and its status; the
  * documents the device leaves undecided are decoded by the host codec in place

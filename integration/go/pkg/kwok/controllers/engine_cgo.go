@@ -17,6 +17,7 @@ package controllers
 #include <stdlib.h>
 #include "kwok_engine.h"
 #include "kwok_watch.h"
+#include "kwok_canon.h"
 */
 import "C"
 
@@ -805,6 +806,31 @@ func (g *gpuEngine) nodeBind(handles []int32, uids []string) (int, error) {
 		return 0, fmt.Errorf("kwok_node_bind: %d: %s", int(rc), g.lastError())
 	}
 	return int(bad), nil
+}
+
+// ---- node status blobs canonicalised on the device (kwok_canon.h, DESIGN.md §28) ----
+
+// canonEnable: kwok_canon_enable (idempotent): the device node decodes write the canonical addresses /
+// allocatable / capacity of every document whose blobs are inside the device domain; the host codec decodes
+// only the others.
+func (g *gpuEngine) canonEnable(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	if rc := C.kwok_canon_enable(g.h, v); rc != C.KWOK_OK {
+		return fmt.Errorf("kwok_canon_enable: %d: %s", int(rc), g.lastError())
+	}
+	return nil
+}
+
+// canonDocs: kwok_canon_stats' docs - node documents canonicalised on the device so far
+func (g *gpuEngine) canonDocs() uint64 {
+	var out [C.KWOK_CANON_STAT_COUNT]C.uint64_t
+	if rc := C.kwok_canon_stats(g.h, &out[0]); rc != C.KWOK_OK {
+		return 0
+	}
+	return uint64(out[C.KWOK_CANON_STAT_DOCS])
 }
 
 // ---- the echo ledger (kwok_watch.h, DESIGN.md §24) ----

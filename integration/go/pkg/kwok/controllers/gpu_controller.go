@@ -260,6 +260,10 @@ type GPUController struct {
 	// nodes' uids from kwok_refs_lookup)
 	nodeDir     bool
 	gpuCodec    bool // pod documents decoded on the GPU (kwok_ingest_pods_json); KWOK_GPU_CODEC=0: the host codec
+	// nodeStatusGPU (KWOK_NODE_STATUS_GPU=1, with the GPU codec): the device canonicalises the status blobs of
+	// the node documents it decodes (kwok_canon.h, DESIGN.md §28): a relist of nodes kwok has patched leaves
+	// no document to the host codec
+	nodeStatusGPU bool
 	podDocsHost int  // pod documents the GPU codec left to the host codec (logged)
 	nodeDocsHost int // node documents the GPU codec left to the host codec (logged)
 }
@@ -326,15 +330,30 @@ func newGPUController(conf Config, interval time.Duration) (*GPUController, erro
 			return nil, err
 		}
 	}
+	gpuCodecOn := os.Getenv("KWOK_GPU_CODEC") != "0"
+	nodeStatusGPU := os.Getenv("KWOK_NODE_STATUS_GPU") == "1"
+	if nodeStatusGPU {
+		if !gpuCodecOn {
+			codec.close()
+			eng.close()
+			return nil, fmt.Errorf("KWOK_NODE_STATUS_GPU=1 needs the GPU codec (KWOK_GPU_CODEC is 0)")
+		}
+		if err := eng.canonEnable(true); err != nil {
+			codec.close()
+			eng.close()
+			return nil, err
+		}
+	}
 	return &GPUController{
 		byUID: byUID, refDir: refDir, nodeDir: nodeDir, batchRefs: map[types.UID]types.NamespacedName{},
+		nodeStatusGPU: nodeStatusGPU,
 		conf: conf, eng: eng, codec: codec, interval: interval, finalizer: finalizerPatch(),
 		nodeName: map[int32]string{}, nodeHandle: map[string]int32{}, podByUID: map[types.UID]int32{},
 		podUID: map[int32]types.UID{},
 		podRef: map[int32]types.NamespacedName{},
 		echo:     echoes{rv: map[types.UID][]string{}, ledger: ledger},
 		queued:   map[types.UID]struct{}{},
-		gpuCodec: os.Getenv("KWOK_GPU_CODEC") != "0",
+		gpuCodec: gpuCodecOn,
 	}, nil
 }
 

@@ -139,6 +139,7 @@ REFS_HEARTBEAT, REFS_NODE_INIT, REFS_POD_PATCH, REFS_DELETE = range(4)  # KWOK_R
 REFS_STATS = ("binds", "notes", "unnamed", "reads", "not_found", "bytes")  # KWOK_REFS_STAT_* order
 NODE_DIR_STATS = ("lookups", "hits", "notes", "binds", "unbound", "bytes")  # KWOK_NODE_DIR_STAT_* order
 RESP_STATS = ("frames", "host_frames", "bytes", "note_calls", "notes")  # KWOK_RESP_STAT_* order (patch responses)
+CANON_STATS = ("docs", "blobs", "bytes_in", "bytes_out", "docs_host", "calls")  # KWOK_CANON_STAT_* order (kwok_canon.h)
 
 
 class Ref(C.Structure):

@@ -72,6 +72,10 @@ responses bytes too: the clientset's patch_*_raw methods return each patch's res
 body, a tick's bodies are framed on the GPU (kwok_frame_responses_gpu), the echo notes
 are taken from the frames (kwok_echo_note_framed) and step 6's pods re-enter from the
 resident bytes (kwok_ingest_pods_framed_uid): DESIGN.md §27.
+
+node_status_gpu=True lets the device canonicalise the status blobs of the node
+documents it decodes (kwok_canon_enable, include/kwok_canon.h): a node kwok has
+patched - every node of a relist - is decoded with no host codec call: DESIGN.md §28.
 """
 from __future__ import annotations
 
@@ -287,6 +291,7 @@ class Stats:
     pod_records: int = 0
     pod_docs_host: int = 0  # pod documents the GPU codec left to the host codec
     node_docs_host: int = 0  # node documents the GPU codec left to the host codec
+    node_docs_canon: int = 0  # node_status_gpu: node documents whose status blobs the device canonicalised
     pod_runs: int = 0
     watch_frames: int = 0       # feed_watch: lines framed
     watch_host_frames: int = 0  # ... of them by the host framer (an escaped type or routed key)
@@ -321,7 +326,7 @@ class Controller:
 
     def __init__(self, conf: Config, backend=None, codec_threads=1, suppress_echoes=True, geometry=None,
                  gpu_codec=True, uid_directory=False, echo_ledger=False, ref_directory=False, node_directory=False,
-                 response_bytes=False):
+                 response_bytes=False, node_status_gpu=False):
         self.conf = conf
         # uid_directory: the engine's pod uid directory (kwok_watch.h) resolves metadata.uid -> handle on
         # the device; pod_by_uid stays empty (a uid the directory cannot key - empty, escaped in the
@@ -388,6 +393,14 @@ class Controller:
                 raise ValueError("response_bytes needs the engine backend (kwok_frame_responses_gpu)")
         self.rq = self._new_responses()
         self.reentered_dev = 0  # response_bytes: pods that re-entered from the resident response bytes (step 6)
+        # node_status_gpu: the device canonicalises the status blobs of the node documents it decodes
+        # (kwok_canon.h): a node kwok has patched, seen again through a relist, is decoded with no
+        # host codec call (stats.node_docs_host counts only the documents outside the device domain)
+        self.node_status_gpu = bool(node_status_gpu)
+        if self.node_status_gpu:
+            if not hasattr(self.eng, "canon_enable"):
+                raise ValueError("node_status_gpu needs the engine backend (kwok_canon_enable)")
+            self.eng.canon_enable()
         self.codec = Codec(manage_all_nodes=conf.manage_all_nodes,
                            manage_nodes_with_annotation_selector=conf.manage_nodes_with_annotation_selector,
                            manage_nodes_with_label_selector=conf.manage_nodes_with_label_selector,
@@ -601,6 +614,13 @@ class Controller:
             else:
                 self._node_put(int(hs[k]), names[k])
 
+    def _count_node_docs(self, nh):
+        """a device node decode: the documents its host codec decoded and, with node_status_gpu, the
+        documents canonicalised on the device so far (kwok_canon_stats' docs)"""
+        self.stats.node_docs_host += nh
+        if self.node_status_gpu:
+            self.stats.node_docs_canon = self.eng.canon_stats()["docs"]
+
     def _flush_nodes_gpu(self, ws, docs):
         """gpu_controller.go flushNodes on the device codec: the documents straight to
         kwok_ingest_nodes_json (a Deleted event's status is not read); names from the
@@ -608,7 +628,7 @@ class Controller:
         arena, offs, lens = Engine._docs(docs)
         ops = np.array([abi.OP_DELETE if w.deleted else abi.OP_UPSERT for w in ws], np.uint8)
         hs, st, nh = self.eng.ingest_nodes_json(self.codec, arena, offs, lens, ops)
-        self.stats.node_docs_host += nh
+        self._count_node_docs(nh)
         self.stats.node_records += int(np.isin(st, (abi.EDOMAIN, abi.EINVAL), invert=True).sum())
         bound = {}  # node_directory: handle -> the uid of its last upsert (a typed event carries none to the device)
         for k, w in enumerate(ws):
@@ -927,7 +947,7 @@ class Controller:
         partial = (abi.EDOMAIN, abi.EINVAL, abi.EFULL)  # a rejected record: the session's picture is partial
         if nodes:
             hs, st, nh = self.eng.ingest_nodes_framed(self.codec, sid, keep)
-            self.stats.node_docs_host += nh
+            self._count_node_docs(nh)
             self.stats.node_records += int(np.isin(st, (abi.EDOMAIN, abi.EINVAL), invert=True).sum())
             for k, i in enumerate(keep):
                 if st[k] != abi.OK:
@@ -1033,7 +1053,7 @@ class Controller:
                 self.eng.resync_mark(kind, marks)
         keep = np.nonzero(ing & (st != abi.ECHO))[0]
         if nodes:
-            self.stats.node_docs_host += nh
+            self._count_node_docs(nh)
             self.stats.node_records += int(np.isin(st[keep], (abi.EDOMAIN, abi.EINVAL), invert=True).sum())
             if self.node_dir:  # the device keeps name, handle and uid of every record: only the rejected ones are looked at
                 keep = keep[st[keep] != abi.OK]

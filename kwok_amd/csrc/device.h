@@ -293,6 +293,19 @@ struct JsonPodSide {
 constexpr int32_t JSON_HOST = 1;  // outside what the device scanner decides: the host codec decodes it
 constexpr int32_t JSON_SPEC = 2;  // decoded; its pod spec is not registered yet (the host registers it)
 constexpr int32_t JSON_SPEC_X = 3;  // decoded; its spec key is a registered spec's, its strings are not (the host decodes it)
+// the node status blob canonicaliser (json.hip k_canon, kwok_canon.h)
+struct CanonCounters {
+    uint32_t n;         // documents on the canon list
+    uint32_t pad;
+    uint64_t raw;       // the raw bytes of their blobs (the size of the canonical buffer)
+};
+struct CanonDoc {       // per listed document: its three blobs (addresses, allocatable, capacity) in the canonical buffer
+    uint64_t off[3];
+    uint32_t len[3];    // 0: the blob is absent, or the document is unclean (nothing of it counts)
+    uint32_t raw[3];    // the raw lengths (statistics)
+    uint32_t doc;       // the batch index
+    uint32_t host;      // 1: a blob outside the device domain - the document went to the host list
+};
 
 // ---- node directory (device-authoritative, ingest.hip) -------------------------
 // A node slot's name lives on the device: node_key[slot] = fnv1a32(name) | len << 32

@@ -1056,7 +1056,10 @@ int node_reserve(kwok_engine* e, size_t n, size_t arena_len) {
 // a custom node template): the string checks and the init blob (node.init.tpl /
 // Config.NodeInitializationTemplate), CONFORMS (A.5).  Host string work, on the
 // partition threads; blob interning under blob_mu.
-NodeFix complete_node(kwok_engine* e, const kwok_node_event& x, uint32_t idx, const char* arena, std::mutex& blob_mu) {
+// cd (kwok_canon.h): the record's blob spans are the raw values of a document the device canonicalised;
+// the canonical bytes are cd's, in cbytes.
+NodeFix complete_node(kwok_engine* e, const kwok_node_event& x, uint32_t idx, const char* arena, std::mutex& blob_mu,
+                      const CanonDoc* cd = nullptr, const char* cbytes = nullptr) {
     NodeFix f{};
     f.idx = idx;
     int st = KWOK_OK;
@@ -1070,7 +1073,8 @@ NodeFix complete_node(kwok_engine* e, const kwok_node_event& x, uint32_t idx, co
     const kwok_str* jr[3] = {&x.addresses, &x.allocatable, &x.capacity};
     for (int k = 0; k < 3 && st == KWOK_OK; k++)
         if (jr[k]->len) {
-            js[k].assign(arena + jr[k]->off, jr[k]->len);
+            if (cd) js[k].assign(cbytes + cd->off[k], cd->len[k]);
+            else js[k].assign(arena + jr[k]->off, jr[k]->len);
             if (!valid_json_blob(js[k].data(), js[k].size(), k == 0 ? '[' : '{')) st = KWOK_EDOMAIN;
         }
     if (st == KWOK_OK) {
@@ -1114,6 +1118,7 @@ struct NodeJsonCtx {
     const std::unordered_map<uint32_t, uint32_t>* hdoc;  // document -> its host decode (hrec / hbuf)
     const std::vector<kwok_node_event>* hrec;     // host-decoded records, spans into their hbuf
     const std::vector<std::string>* hbuf;
+    const kwok_engine::Canon* canon = nullptr;    // the decode's device-canonicalised documents (kwok_canon.h), or null
 };
 int ingest_nodes_impl(kwok_engine* e, const kwok_node_event* ev, size_t n, const char* arena, size_t arena_len,
                       int32_t* out_handles, int32_t* out_status, const NodeJsonCtx* nj);
@@ -1231,9 +1236,13 @@ int ingest_nodes_impl(kwok_engine* e, const kwok_node_event* ev, size_t n, const
                     continue;
                 }
                 auto h = nj->hdoc->find(idx[k]);
-                fix[k] = h == nj->hdoc->end()
-                             ? complete_node(e, dev_rec[k], idx[k], nj->arena, blob_mu)
-                             : complete_node(e, (*nj->hrec)[h->second], idx[k], (*nj->hbuf)[h->second].data(), blob_mu);
+                if (h != nj->hdoc->end()) {
+                    fix[k] = complete_node(e, (*nj->hrec)[h->second], idx[k], (*nj->hbuf)[h->second].data(), blob_mu);
+                    continue;
+                }
+                // (a document the device canonicalised: its blobs from the canonical buffer, never the document's)
+                const CanonDoc* cd = nj->canon ? nj->canon->find(idx[k]) : nullptr;
+                fix[k] = complete_node(e, dev_rec[k], idx[k], nj->arena, blob_mu, cd, cd ? nj->canon->bytes_h.data() : nullptr);
             }
         });
         if ((rc = upload_blobs(e))) return rc;
@@ -1958,11 +1967,98 @@ uint64_t kwok_spec_key(const kwok_pod_spec* spec, const char* arena, size_t aren
 // the documents the scanner lists (a non-empty addresses / allocatable /
 // capacity blob, whose canonical form is the host's, or an escaped routed
 // string), then kwok_ingest_nodes' GPU event switch over the records, which
-// stay on the device.
+// stay on the device.  With kwok_canon_enable the blobs of a document inside the
+// device domain are canonicalised there (json_nodes_canon): no host codec call.
 namespace {
+// ---- the status blob canonicaliser (kwok_canon.h, json.hip k_canon) ----
+// Before a scan of n documents with the switch on: the canon list and the counters, zeroed.
+int canon_reserve(kwok_engine* e, size_t n) {
+    auto& C = e->canon;
+    if (!C.ctr) {
+        if (int rc = dalloc(e, &C.ctr, 1)) return rc;
+        if (hipHostMalloc((void**)&C.ctr_h.p, sizeof(CanonCounters), hipHostMallocDefault) != hipSuccess)
+            return e->fail(KWOK_ENOMEM, "canonicaliser staging");
+    }
+    if (int rc = C.docs.reserve(e, n)) return rc;
+    HIPCHK(e, hipMemsetAsync(C.ctr, 0, sizeof(CanonCounters), e->st));
+    return KWOK_OK;
+}
+// Behind the scan's launches (every piece of d_arena has landed before the last of them): the listed count
+// comes back; if there is any, the raw lengths, their scan, k_canon over the list, then the pairs and the
+// canonical bytes to the host (canon.doc_h sorted by document, canon.bytes_h).  The documents k_canon found
+// outside its domain are on json.host_list with status JSON_HOST when it returns.  Synchronises.
+int json_nodes_canon(kwok_engine* e, const uint8_t* d_arena) {
+    auto& C = e->canon;
+    auto& J = e->json;
+    hipStream_t st = e->st;
+    const auto t0 = clk::now();
+    HIPCHK(e, hipMemcpyAsync(C.ctr_h, C.ctr, sizeof(CanonCounters), hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    const uint32_t nc = C.ctr_h->n;
+    const uint64_t raw = C.ctr_h->raw;
+    if (!nc) return KWOK_OK;
+    if (nc > C.docs.cap) return e->fail(KWOK_EDEVICE, "canonicaliser: %u documents listed, room for %zu", nc, C.docs.cap);
+    int rc = 0;
+    if ((rc = C.out.reserve(e, (size_t)raw))) return rc;
+    const size_t tmp = refs_scan_bytes(nc);
+    if (tmp > C.tmp_bytes) {
+        C.tmp.release(), C.tmp_bytes = 0;
+        const size_t want = tmp + tmp / 4 + 256;
+        if (hipMalloc(&C.tmp.p, want) != hipSuccess) return e->fail(KWOK_ENOMEM, "canonicaliser: scan storage");
+        C.tmp_bytes = want;
+    }
+    ProfEvents<2> pev(e->iprof, st);
+    pev.stamp(0);
+    launch_canon_len(e->ing.d_nev, C.list, nc, C.len, st);
+    if (launch_scan64(C.len, C.off, nc, C.tmp, C.tmp_bytes, st)) return e->fail(KWOK_EDEVICE, "canonicaliser: scan");
+    CanonArgs A{};
+    A.arena = d_arena;
+    A.ev = e->ing.d_nev;
+    A.status = J.nstat;
+    A.list = C.list;
+    A.n = nc;
+    A.off = C.off;
+    A.out = C.bytes;
+    A.docs = C.doc;
+    A.host_list = J.host_list;
+    A.n_host = J.n_host;
+    launch_canon(A, st);
+    HIPCHK(e, hipGetLastError());
+    pev.stamp(1);
+    C.doc_h.resize(nc);
+    C.bytes_h.resize((size_t)raw);
+    HIPCHK(e, hipMemcpyAsync(C.doc_h.data(), C.doc, (size_t)nc * sizeof(CanonDoc), hipMemcpyDeviceToHost, st));
+    if (raw) HIPCHK(e, hipMemcpyAsync(C.bytes_h.data(), C.bytes, (size_t)raw, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    std::sort(C.doc_h.begin(), C.doc_h.end(), [](const CanonDoc& a, const CanonDoc& b) { return a.doc < b.doc; });
+    uint64_t docs = 0, blobs = 0, in = 0, out = 0;
+    for (const CanonDoc& d : C.doc_h) {
+        if (d.host) continue;
+        docs++;
+        for (int j = 0; j < 3; j++) {
+            if ((uint64_t)d.off[j] + d.len[j] > raw || d.len[j] > d.raw[j])
+                return e->fail(KWOK_EDEVICE, "canonicaliser: a blob outside the canonical buffer");
+            blobs += d.len[j] != 0, in += d.len[j] ? d.raw[j] : 0, out += d.len[j];
+        }
+    }
+    C.stats[KWOK_CANON_STAT_DOCS] += docs;
+    C.stats[KWOK_CANON_STAT_BLOBS] += blobs;
+    C.stats[KWOK_CANON_STAT_BYTES_IN] += in;
+    C.stats[KWOK_CANON_STAT_BYTES_OUT] += out;
+    C.stats[KWOK_CANON_STAT_DOCS_HOST] += nc - docs;
+    C.stats[KWOK_CANON_STAT_CALLS]++;
+    if (e->iprof)
+        fprintf(stderr, "[kwok canon]  %u documents listed, %llu canonicalised (%llu blobs, %llu -> %llu bytes), %llu to the host: "
+                        "lengths + scan + k_canon %.3f ms on the device, the call %.3f ms\n", nc, (unsigned long long)docs,
+                (unsigned long long)blobs, (unsigned long long)in, (unsigned long long)out, (unsigned long long)(nc - docs),
+                pev.elapsed(0, 1), ms_between(t0, clk::now()));
+    return KWOK_OK;
+}
 // documents [0, n) decoded on the device: records in ing.d_nev (op: the caller's, or
 // KWOK_OP_UPSERT when op is null; 0xFF for a document not decided there), the
-// decode statuses into dstat, the number listed for the host (json.host_list) in *nh
+// decode statuses into dstat, the number listed for the host (json.host_list) in *nh.
+// With the canonicaliser on a record holds its blobs' raw spans; the canonical bytes
+// are in canon.doc_h / bytes_h
 int json_nodes_decode(kwok_engine* e, const kwok_codec* c, const char* arena, size_t arena_len, const uint64_t* doc_off,
                       const uint32_t* doc_len, const uint8_t* op, size_t n, std::vector<int32_t>& dstat, uint32_t* nh,
                       const uint8_t* resident = nullptr) {  // (resident: as json_decode's)
@@ -1973,6 +2069,9 @@ int json_nodes_decode(kwok_engine* e, const kwok_codec* c, const char* arena, si
     auto& G = e->ing;
     auto& J = e->json;
     if ((rc = J.node_docs.reserve(e, n))) return rc;
+    auto& C = e->canon;
+    C.doc_h.clear();
+    if (C.on && (rc = canon_reserve(e, n))) return rc;
     hipStream_t st = e->st, ps = G.pst;
     if ((rc = codec_export(c, J.cfg_h))) {  // (selectors beyond the device tables: every document to the host)
         if (rc != KWOK_EDOMAIN) return e->fail(rc, "%s", kwok_codec_last_error());
@@ -2014,9 +2113,12 @@ int json_nodes_decode(kwok_engine* e, const kwok_codec* c, const char* arena, si
         A.host_list = J.host_list;
         A.n_host = J.n_host;
         A.base = (uint32_t)d0;
+        A.canon_list = C.on ? C.list.p : nullptr;
+        A.canon_ctr = C.ctr;
         launch_json_nodes(A, st);
         HIPCHK(e, hipGetLastError());
     }
+    if (C.on && (rc = json_nodes_canon(e, resident ? resident : G.d_arena))) return rc;
     const auto tq = clk::now();
     dstat.resize(n);
     HIPCHK(e, hipMemcpyAsync(dstat.data(), J.nstat, n * 4, hipMemcpyDeviceToHost, st));
@@ -2094,7 +2196,8 @@ int nodes_complete_listed(kwok_engine* e, const kwok_codec* c, const char* arena
 // the documents the scanner lists (a non-empty addresses / allocatable /
 // capacity blob, whose canonical form is the host's, or an escaped routed
 // string), then kwok_ingest_nodes' GPU event switch over the records, which
-// stay on the device.
+// stay on the device.  With kwok_canon_enable the blobs of a document inside the
+// device domain are canonicalised there (json_nodes_canon): no host codec call.
 namespace {
 int ingest_nodes_json_impl(kwok_engine* e, const kwok_codec* c, const char* arena, size_t arena_len,
                            const uint64_t* doc_off, const uint32_t* doc_len, const uint8_t* op, size_t n,
@@ -2145,7 +2248,7 @@ int ingest_nodes_json_impl(kwok_engine* e, const kwok_codec* c, const char* aren
     if (e->iprof)
         fprintf(stderr, "[kwok json] %zu node documents decoded on the GPU (%u by the host): %.2f ms\n", n, nh,
                 ms_between(t0, clk::now()));
-    NodeJsonCtx ctx{arena, &hdoc, &hrec, &hbuf};
+    NodeJsonCtx ctx{arena, &hdoc, &hrec, &hbuf, e->canon.on ? &e->canon : nullptr};
     std::vector<int32_t> stat(out_status ? 0 : n);
     int32_t* so = out_status ? out_status : stat.data();
     rc = ingest_nodes_impl(e, nullptr, n, arena, arena_len, out_handles, so, &ctx);
@@ -2184,6 +2287,17 @@ int kwok_decode_nodes_gpu(kwok_engine* e, const kwok_codec* c, char* arena, size
         kwok_node_event x{};
         dstat[i] = kwok_decode_node(c, arena, arena_len, doc_off[i], doc_len[i], &x);
         ev[i] = x;
+    }
+    // the documents the device canonicalised (kwok_canon.h): each blob over the start of its own span in the
+    // caller's arena, the record's length the canonical one - what kwok_decode_node writes
+    for (const CanonDoc& d : e->canon.doc_h) {
+        if (d.host || d.doc >= n) continue;
+        kwok_str* s[3] = {&ev[d.doc].addresses, &ev[d.doc].allocatable, &ev[d.doc].capacity};
+        for (int j = 0; j < 3; j++) {
+            if (!d.len[j] || (uint64_t)s[j]->off + s[j]->len > arena_len || d.len[j] > s[j]->len) continue;
+            memcpy(arena + s[j]->off, e->canon.bytes_h.data() + d.off[j], d.len[j]);
+            s[j]->len = d.len[j];
+        }
     }
     int bad = 0;
     for (size_t i = 0; i < n; i++) {
@@ -2526,6 +2640,21 @@ int kwok_frame_responses_gpu(kwok_engine* e, const char* buf, size_t len, const 
 int kwok_response_stats(kwok_engine* e, uint64_t out[KWOK_RESP_STAT_COUNT]) {
     if (!e || !out) return KWOK_EINVAL;
     for (int k = 0; k < KWOK_RESP_STAT_COUNT; k++) out[k] = e->watch.rstats[k];
+    return KWOK_OK;
+}
+
+// ---- node status blobs canonicalised on the device (kwok_canon.h): the switch and its counters;
+// the work is json_nodes_canon's, behind every device node decode ----
+int kwok_canon_enable(kwok_engine* e, int on) {
+    if (!e) return KWOK_EINVAL;
+    if (e->poisoned) return poisoned(e);
+    e->canon.on = on != 0;  // (the buffers come with the first decode that needs them)
+    return KWOK_OK;
+}
+
+int kwok_canon_stats(const kwok_engine* e, uint64_t out[KWOK_CANON_STAT_COUNT]) {
+    if (!e || !out) return KWOK_EINVAL;
+    for (int k = 0; k < KWOK_CANON_STAT_COUNT; k++) out[k] = e->canon.stats[k];
     return KWOK_OK;
 }
 
@@ -3518,6 +3647,9 @@ int nodes_framed_dev_impl(kwok_engine* e, const kwok_codec* c, const uint32_t* d
     int rc = 0;
     if ((rc = node_reserve(e, n, 0)) || (rc = json_reserve(e, n)) || (rc = J.node_docs.reserve(e, n)) || (rc = D.recs.reserve(e, n)))
         return rc;
+    auto& C = e->canon;
+    C.doc_h.clear();
+    if (C.on && (rc = canon_reserve(e, n))) return rc;
     if ((rc = codec_export(c, J.cfg_h))) {  // (selectors beyond the device tables: every document to the host)
         if (rc != KWOK_EDOMAIN) return e->fail(rc, "%s", kwok_codec_last_error());
         memset(J.cfg_h, 0, sizeof(JsonCfg));
@@ -3540,8 +3672,11 @@ int nodes_framed_dev_impl(kwok_engine* e, const kwok_codec* c, const uint32_t* d
     A.host_list = J.host_list;
     A.n_host = J.n_host;
     A.base = 0;
+    A.canon_list = C.on ? C.list.p : nullptr;
+    A.canon_ctr = C.ctr;
     launch_json_nodes(A, st);
     HIPCHK(e, hipGetLastError());
+    if (C.on && (rc = json_nodes_canon(e, Wt.stream))) return rc;
     HIPCHK(e, hipMemcpyAsync(J.n_host_h, J.n_host, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipMemcpyAsync(D.call_h, D.call, sizeof(*D.call_h.p), hipMemcpyDeviceToHost, st));
     HIPCHK(e, hipStreamSynchronize(st));
@@ -3575,7 +3710,7 @@ int nodes_framed_dev_impl(kwok_engine* e, const kwok_codec* c, const uint32_t* d
     const NodeUidNote un{Wt.stream, Wt.len, D.uoff, D.ulen};
     ScopedPtr<NodeUidNote> uids(D.note, &un);
     ScopedPtr<uint8_t> src(G.arena_src, Wt.stream);  // the ingest kernels read the batch's strings from the resident stream
-    NodeJsonCtx ctx{Wt.host, &hdoc, &hrec, &hbuf};
+    NodeJsonCtx ctx{Wt.host, &hdoc, &hrec, &hbuf, e->canon.on ? &e->canon : nullptr};
     return ingest_nodes_impl(e, nullptr, n, Wt.host, Wt.len, nullptr, nullptr, &ctx);
 }
 }  // namespace

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/kwok_engine.h"
+#include "../../include/kwok_canon.h"
 #include "codec.h"
 #include "device.h"
 #include "gotemplate.h"
@@ -438,6 +439,31 @@ struct kwok_engine {
         uint32_t tab_mask = 0;
         bool tab_dirty = true;
     } json;
+
+    // ---- node status blobs canonicalised on the device (json.hip k_canon, kwok_canon.h): nothing is
+    // allocated before the first node decode with the switch on ----
+    struct KWOK_LOCAL Canon {
+        bool on = false;
+        DevArr<CanonCounters> ctr;         // [1] the scan's: listed documents, their raw blob bytes
+        Pinned<CanonCounters> ctr_h;
+        DevArr<uint32_t> list;             // [docs.cap] the canon list (batch indices, in the order the scan appended them)
+        DevArr<uint64_t> len, off;         // [docs.cap] raw blob bytes per listed document, their exclusive scan
+        DevArr<CanonDoc> doc;              // [docs.cap] per listed document: its three (offset, length) pairs
+        DevGroup docs{4096, {list, len, off, doc}};
+        DevArr<uint8_t> bytes;             // the compact canonical bytes of the call
+        DevGroup out{1 << 16, {bytes}};
+        DevArr<void> tmp;                  // [tmp_bytes] the scan's storage (not zero-filled)
+        size_t tmp_bytes = 0;
+        // the last decode's result on the host: the listed documents sorted by batch index, and the bytes
+        std::vector<CanonDoc> doc_h;
+        std::vector<char> bytes_h;
+        uint64_t stats[KWOK_CANON_STAT_COUNT] = {};
+        // the clean document i of the last decode, or null
+        const CanonDoc* find(uint32_t i) const {
+            auto it = std::lower_bound(doc_h.begin(), doc_h.end(), i, [](const CanonDoc& d, uint32_t v) { return d.doc < v; });
+            return it != doc_h.end() && it->doc == i && !it->host ? &*it : nullptr;
+        }
+    } canon;
     std::unordered_map<uint64_t, int32_t> spec_keys;  // kwok_spec_key -> spec id (-2: two specs share the key)
     std::unordered_map<uint64_t, std::string> spec_canon;  // kwok_spec_key -> the canonical string of its spec
 

@@ -1058,14 +1058,24 @@ void launch_json_pods(const JsonPodArgs& A, hipStream_t st) {
 // listed for the host (JSON_HOST), as is any string the scan would have to
 // compare as decoded text (an escaped routed key, label key or compared value).
 // kwok's own fleets create Nodes with an empty status: none of them is listed.
+// With the status blob canonicaliser on (kwok_canon.h; k_json_nodes_canon and
+// k_canon below) a non-empty blob lists the document for k_canon instead, which
+// writes the canonical form on the device or hands the document to the host.
 // ---------------------------------------------------------------------------
 enum : uint8_t {
     N_NONE = 0, N_ROOT, N_META, N_STATUS, N_NAME, N_ANN, N_LAB, N_ANNV, N_LABV, N_PHASE, N_ADDR, N_ALLOC, N_CAP,
     N_INFO, N_INFOV,
 };
-struct NodeScan {
+// CANON (the status blob canonicaliser on, kwok_canon.h): a non-empty blob does not list the
+// document for the host; the scan notes which blobs hold a member (ne) and the raw span of each
+// value, and k_canon (below) decides the document.  Named fields, no indexed span: the scan state
+// stays in registers.
+template <bool CANON>
+struct NodeScanT {
     JRd* r;
     const JsonCfg* cfg;
+    uint32_t ne = 0;           // CANON: bit k - blob k (addresses, allocatable, capacity) holds a member
+    Span b_addr{0, 0}, b_alloc{0, 0}, b_cap{0, 0};  // CANON: the blobs' raw value spans
     uint64_t cx = 0;
     uint8_t next = N_NONE;
     uint8_t info_k = 0;   // the nodeInfo key the next value belongs to
@@ -1126,6 +1136,10 @@ struct NodeScan {
         const uint8_t c = ctx(d);
         next = N_NONE;
         if (c == N_NONE) return;
+        if (CANON && (c == N_ALLOC || c == N_CAP)) {  // a member, whatever its key: k_canon reads the blob
+            ne |= c == N_ALLOC ? 2u : 4u;
+            return;
+        }
         if (c == N_ANN || c == N_LAB) {  // a label / annotation entry
             const bool ann = c == N_ANN;
             if (ann) n_ann++;  // (no reference picked by a condition: the scan's state stays in registers)
@@ -1195,7 +1209,10 @@ struct NodeScan {
     __device__ void scalar(int d, const JTok& t, bool pa) {
         const uint8_t c = value_ctx(d, pa);
         if (d == 0) return;
-        if (pa && ctx(d - 1) == N_ADDR) host = true;  // a non-empty addresses list (canonical: the host codec's)
+        if (pa && ctx(d - 1) == N_ADDR) {  // a non-empty addresses list (canonical: the host codec's, or k_canon's)
+            if (CANON) ne |= 1u;
+            else host = true;
+        }
         switch (c) {
             case N_META: err = KWOK_EDOMAIN; break;  // metadata must be an object (null included)
             case N_NAME: ref(t, name); break;
@@ -1259,7 +1276,10 @@ struct NodeScan {
             set_ctx(0, a ? N_NONE : N_ROOT);
             return;
         }
-        if (pa && ctx(d - 1) == N_ADDR) host = true;
+        if (pa && ctx(d - 1) == N_ADDR) {
+            if (CANON) ne |= 1u;
+            else host = true;
+        }
         switch (c) {
             case N_META: if (a) err = KWOK_EDOMAIN; else mine = N_META, meta_obj = true; break;
             case N_STATUS: if (!a) mine = N_STATUS; break;  // (a status that is no object is ignored)
@@ -1271,8 +1291,22 @@ struct NodeScan {
             default: break;
         }
         set_ctx(d, mine);
+        if (CANON) {  // the value's '[' / '{' (selects of values: a store picked by a condition would index the spans)
+            const uint32_t p = (uint32_t)(r->pos - 1);
+            b_addr.off = mine == N_ADDR ? p : b_addr.off;
+            b_alloc.off = mine == N_ALLOC ? p : b_alloc.off;
+            b_cap.off = mine == N_CAP ? p : b_cap.off;
+        }
     }
-    __device__ void end(int, bool, bool) {}  // (a blob was listed at its first member; an empty one is absent)
+    // (a blob was listed at its first member; an empty one is absent.  CANON: the value ends here)
+    __device__ void end(int d, bool, bool) {
+        if (!CANON) return;
+        const uint8_t c = ctx(d);
+        const uint32_t p = (uint32_t)r->pos;
+        b_addr.len = c == N_ADDR ? p - b_addr.off : b_addr.len;
+        b_alloc.len = c == N_ALLOC ? p - b_alloc.off : b_alloc.len;
+        b_cap.len = c == N_CAP ? p - b_cap.off : b_cap.len;
+    }
     __device__ bool matches(const JsonSel& S, const SelState& st) const {
         for (uint32_t q = 0; q < S.nreq; q++) {
             const bool has = (st.has >> q) & 1, in = (st.in >> q) & 1;
@@ -1288,7 +1322,8 @@ struct NodeScan {
 };
 
 // one thread per node document; op[i]: the caller's watch event (the record's op)
-__global__ __launch_bounds__(256) void k_json_nodes(JsonNodeArgs A) {
+template <bool CANON>
+__device__ __forceinline__ void json_node_doc(const JsonNodeArgs& A) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= A.n) return;
     const uint64_t off = A.doc_off[i];
@@ -1300,7 +1335,7 @@ __global__ __launch_bounds__(256) void k_json_nodes(JsonNodeArgs A) {
     ev.name = ev.addresses = ev.allocatable = ev.capacity = kwok_str{0, 0};
     for (int k = 0; k < KWOK_NI_COUNT; k++) ev.node_info[k] = kwok_str{0, 0};
     int32_t status;
-    NodeScan p;
+    NodeScanT<CANON> p;
     for (int k = 0; k < KWOK_NI_COUNT; k++) p.info[k] = Span{0, 0};
     if (off > A.arena_len || len > A.arena_len - off) {
         status = KWOK_EINVAL;  // (codec.cpp parse_doc: a span outside the arena)
@@ -1329,6 +1364,15 @@ __global__ __launch_bounds__(256) void k_json_nodes(JsonNodeArgs A) {
             ev.phase = p.phase;
             ev.name = kwok_str{p.name.off, p.name.len};
             for (int k = 0; k < KWOK_NI_COUNT; k++) ev.node_info[k] = kwok_str{p.info[k].off, p.info[k].len};
+            if (CANON && p.ne) {  // the raw spans of the non-empty blobs: k_canon decides the document
+                const uint32_t m0 = p.ne & 1u ? ~0u : 0u, m1 = p.ne & 2u ? ~0u : 0u, m2 = p.ne & 4u ? ~0u : 0u;
+                ev.addresses = kwok_str{p.b_addr.off & m0, p.b_addr.len & m0};
+                ev.allocatable = kwok_str{p.b_alloc.off & m1, p.b_alloc.len & m1};
+                ev.capacity = kwok_str{p.b_cap.off & m2, p.b_cap.len & m2};
+                A.canon_list[atomicAdd(&A.canon_ctr->n, 1u)] = A.base + i;
+                atomicAdd(reinterpret_cast<unsigned long long*>(&A.canon_ctr->raw),
+                          (unsigned long long)ev.addresses.len + ev.allocatable.len + ev.capacity.len);
+            }
         }
     }
     if (status != KWOK_OK) ev.op = 0xFF;  // (not applied: the host completes it, or its status is the decode's)
@@ -1336,11 +1380,242 @@ __global__ __launch_bounds__(256) void k_json_nodes(JsonNodeArgs A) {
     A.status[i] = status;
     if (status == JSON_HOST) A.host_list[atomicAdd(A.n_host, 1u)] = A.base + i;
 }
+__global__ __launch_bounds__(256) void k_json_nodes(JsonNodeArgs A) { json_node_doc<false>(A); }
+// ... with the canonicaliser on (A.canon_list set)
+__global__ __launch_bounds__(256) void k_json_nodes_canon(JsonNodeArgs A) { json_node_doc<true>(A); }
 
 void launch_json_nodes(const JsonNodeArgs& A, hipStream_t st) {
     if (!A.n) return;
     const uint32_t bs = json_block(A.n);
-    hipLaunchKernelGGL(k_json_nodes, dim3((A.n + bs - 1) / bs), dim3(bs), 0, st, A);
+    if (A.canon_list) hipLaunchKernelGGL(k_json_nodes_canon, dim3((A.n + bs - 1) / bs), dim3(bs), 0, st, A);
+    else hipLaunchKernelGGL(k_json_nodes, dim3((A.n + bs - 1) / bs), dim3(bs), 0, st, A);
+}
+
+// ---------------------------------------------------------------------------
+// the node status blob canonicaliser (kwok_canon.h): what
+// codec.cpp canon() writes for the addresses / allocatable / capacity values of
+// the documents k_json_nodes_canon listed - members of every object in bytewise
+// key order (a shorter prefix first), `,` and `:` without whitespace, scalars
+// verbatim - into a compact buffer of its own, never into the arena.
+//
+// One lane per listed document, its blobs one after the other, each in one
+// jparse pass over the value's raw span (the scanner accepted the document, so
+// the grammar holds).  The device domain ("clean"): a blob is an array of
+// scalars and of objects of scalars (addresses) or an object of scalars
+// (allocatable, capacity) - CANON_MAX_DEPTH containers deep at the most - with
+// at most CANON_MAX_MEMBERS members per object, no duplicate key, no backslash
+// escape, no byte go_string would change (`<`, `>`, `&`), no byte >= 0x80, every
+// number a plain_int.  Anything else marks the whole document JSON_HOST and
+// appends it to the scanner's host list; nothing of it is used.
+//
+// The per-lane table - an object's key offsets, sorted by insertion when the
+// object closes - lives in LDS, entry e of lane l at tab[e * CANON_BLOCK + l]
+// (a wave's lanes at the same entry hit 64 different banks): 8 KiB per block of
+// one wave, no scratch.  The object is written from the sorted offsets by
+// tokenizing each member again (a second reader: the parse position stays).
+// ---------------------------------------------------------------------------
+constexpr uint32_t CANON_MAX_MEMBERS = 32;  // members of one object
+constexpr int CANON_MAX_DEPTH = 2;          // containers, the blob's own included (addresses: the list, its objects)
+constexpr uint32_t CANON_BLOCK = 64;
+
+namespace {
+__device__ __forceinline__ bool canon_plain_byte(uint32_t c) { return c < 0x80 && c != '<' && c != '>' && c != '&'; }
+
+struct CanonScan {
+    JRd* r;          // the parse
+    JRd* r2;         // the writer's reader
+    uint32_t* tab;   // this lane's column of the block's table
+    uint8_t* out;
+    uint32_t cap, w = 0;  // the blob's raw length (the canonical form is no longer), bytes written
+    bool arr;        // the blob is the addresses list
+    bool bad = false;
+    uint32_t m = 0, elems = 0;  // members of the open object; elements of the list written
+
+    __device__ void put(uint32_t c) {
+        if (w < cap) out[w] = (uint8_t)c;
+        else bad = true;
+        w++;
+    }
+    __device__ void copy(jpos off, uint32_t len) {
+        for (uint32_t k = 0; k < len; k++) put(r2->at(off + k));
+    }
+    __device__ bool clean_str(const JTok& t) {
+        if (t.esc) return false;
+        for (uint32_t k = 0; k < t.len; k++)
+            if (!canon_plain_byte(r->at(t.off + k))) return false;
+        return true;
+    }
+    __device__ bool plain_int(const JTok& t) {  // codec.cpp plain_int
+        uint32_t k = r->at(t.off) == '-' ? 1 : 0;
+        if (k >= t.len) return false;
+        if (r->at(t.off + k) == '0' && t.len > k + 1) return false;
+        for (; k < t.len; k++) {
+            const uint32_t c = r->at(t.off + k);
+            if (c < '0' || c > '9') return false;
+        }
+        return true;
+    }
+    // the keys at a and b (inside their quotes; clean: the closing quote ends each): < 0, 0, > 0 as
+    // std::string_view compares them
+    __device__ int key_cmp(jpos a, jpos b) {
+        for (uint32_t k = 0;; k++) {
+            const uint32_t x = r->at(a + k), y = r2->at(b + k);
+            const bool xe = x == '"', ye = y == '"';
+            if (xe || ye) return xe && ye ? 0 : xe ? -1 : 1;
+            if (x != y) return x < y ? -1 : 1;
+        }
+    }
+    // the object just closed: its members from the table, sorted, each tokenized again and copied
+    __device__ void write_object() {
+        for (uint32_t a = 1; a < m && !bad; a++) {
+            const uint32_t x = tab[a * CANON_BLOCK];
+            uint32_t b = a;
+            while (b > 0) {
+                const uint32_t y = tab[(b - 1) * CANON_BLOCK];
+                const int c = key_cmp(y, x);
+                if (c == 0) bad = true;  // a duplicate key
+                if (c <= 0) break;
+                tab[b * CANON_BLOCK] = y;
+                b--;
+            }
+            tab[b * CANON_BLOCK] = x;
+        }
+        if (bad) return;
+        put('{');
+        for (uint32_t q = 0; q < m; q++) {
+            if (q) put(',');
+            JTok t;
+            r2->pos = tab[q * CANON_BLOCK] - 1;
+            if (!jstring(*r2, t)) {
+                bad = true;
+                return;
+            }
+            copy(t.off - 1, t.len + 2);
+            put(':');
+            for (;;) {  // whitespace, the colon, whitespace
+                const int c = r2->peek();
+                if (c != ' ' && c != '\t' && c != '\n' && c != '\r' && c != ':') break;
+                r2->pos++;
+            }
+            if (r2->peek() == '"') {
+                if (!jstring(*r2, t)) {
+                    bad = true;
+                    return;
+                }
+                copy(t.off - 1, t.len + 2);
+            } else {  // a plain integer, true, false or null: up to the byte that ends it
+                for (;;) {
+                    const int c = r2->peek();
+                    if (c < 0 || c == ',' || c == '}' || c == ' ' || c == '\t' || c == '\n' || c == '\r') break;
+                    put((uint32_t)c);
+                    r2->pos++;
+                }
+            }
+        }
+        put('}');
+    }
+
+    __device__ void key(int, const JTok& t) {
+        if (bad) return;
+        if (!clean_str(t) || m >= CANON_MAX_MEMBERS) {
+            bad = true;
+            return;
+        }
+        tab[m * CANON_BLOCK] = (uint32_t)t.off;
+        m++;
+    }
+    __device__ void scalar(int d, const JTok& t, bool pa) {
+        if (bad) return;
+        if (t.kind == J_STR ? !clean_str(t) : t.kind == J_NUM && !plain_int(t)) {
+            bad = true;
+            return;
+        }
+        if (d == 1 && pa) {  // an element of the list that is no object: verbatim
+            if (elems++) put(',');
+            if (t.kind == J_STR) copy(t.off - 1, t.len + 2);
+            else copy(t.off, t.len);
+        }
+    }
+    __device__ void begin(int d, bool a, bool) {
+        if (bad) return;
+        if (d == 0) {
+            if (a) put('[');
+        } else if (d >= CANON_MAX_DEPTH || !arr || a) {
+            bad = true;  // a container in an object, a list in the list, or deeper
+            return;
+        }
+        m = 0;
+    }
+    __device__ void end(int d, bool a, bool) {
+        if (bad) return;
+        if (a) {
+            put(']');
+            return;
+        }
+        if (d == 1 && elems++) put(',');
+        write_object();
+    }
+};
+}  // namespace
+
+__global__ __launch_bounds__(CANON_BLOCK) void k_canon_len(const kwok_node_event* ev, const uint32_t* list, uint32_t n, uint64_t* lens) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const kwok_node_event& x = ev[list[k]];
+    lens[k] = (uint64_t)x.addresses.len + x.allocatable.len + x.capacity.len;
+}
+
+__global__ __launch_bounds__(CANON_BLOCK) void k_canon(CanonArgs A) {
+    __shared__ uint32_t tab[CANON_MAX_MEMBERS * CANON_BLOCK];
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= A.n) return;
+    const uint32_t i = A.list[k];
+    CanonDoc* D = A.docs + k;  // (written field by field where it lies: no local array, no scratch)
+    uint64_t o = A.off[k];
+    bool bad = false;
+    // blob j of the document: parsed and written at o; its pair (one call site of the parser)
+    const kwok_str b0 = A.ev[i].addresses, b1 = A.ev[i].allocatable, b2 = A.ev[i].capacity;
+    for (int j = 0; j < 3; j++) {
+        const kwok_str raw{j == 0 ? b0.off : j == 1 ? b1.off : b2.off, j == 0 ? b0.len : j == 1 ? b1.len : b2.len};
+        D->off[j] = o;
+        D->raw[j] = raw.len;
+        uint32_t len = 0;
+        if (raw.len && !bad) {
+            JRd rd{A.arena, (jpos)raw.off, (jpos)(raw.off + raw.len), ~0u, make_uint4(0, 0, 0, 0)};
+            JRd r2 = rd;
+            CanonScan h;
+            h.r = &rd, h.r2 = &r2;
+            h.tab = tab + threadIdx.x;
+            h.out = A.out + o;
+            h.cap = raw.len;
+            h.arr = j == 0;
+            if (!jparse(rd, h) || h.bad) bad = true;
+            else len = h.w;
+            o += raw.len;
+        }
+        D->len[j] = len;
+    }
+    D->doc = i;
+    D->host = bad ? 1u : 0u;
+    if (bad) {  // the host decides the whole document, errors included
+        D->len[0] = D->len[1] = D->len[2] = 0;
+        kwok_node_event ev;
+        ev.op = 0xFF;
+        ev.managed = ev.lockable = 0;
+        ev.phase = KWOK_PHASE_NONE;
+        ev.name = ev.addresses = ev.allocatable = ev.capacity = kwok_str{0, 0};
+        for (int q = 0; q < KWOK_NI_COUNT; q++) ev.node_info[q] = kwok_str{0, 0};
+        A.ev[i] = ev;
+        A.status[i] = JSON_HOST;
+        A.host_list[atomicAdd(A.n_host, 1u)] = i;
+    }
+}
+
+void launch_canon_len(const kwok_node_event* ev, const uint32_t* list, uint32_t n, uint64_t* lens, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_canon_len, dim3((n + CANON_BLOCK - 1) / CANON_BLOCK), dim3(CANON_BLOCK), 0, st, ev, list, n, lens);
+}
+void launch_canon(const CanonArgs& A, hipStream_t st) {
+    if (A.n) hipLaunchKernelGGL(k_canon, dim3((A.n + CANON_BLOCK - 1) / CANON_BLOCK), dim3(CANON_BLOCK), 0, st, A);
 }
 
 // node records of a batch gathered for the host (list[k] -> out[k]) / written back (in[k] -> list[k])

@@ -288,8 +288,30 @@ struct JsonNodeArgs {
     uint32_t* host_list;         // [n] out: documents the host codec decodes (JSON_HOST), as base + index
     uint32_t* n_host;            // [1] (zeroed by the caller)
     uint32_t base;               // the batch index of document 0 of this launch (a piece of the batch)
+    // the status blob canonicaliser (kwok_canon.h; null: off, the kernel is the one it was): a document that
+    // is KWOK_OK and holds a non-empty blob is appended here, its record holding the blobs' raw value spans
+    uint32_t* canon_list;        // [n] out, as base + index
+    CanonCounters* canon_ctr;    // [1] (zeroed by the caller)
 };
 void launch_json_nodes(const JsonNodeArgs& A, hipStream_t st);
+// ---- the node status blob canonicaliser (json.hip, kwok_canon.h) ----
+// lens[k] = the raw bytes of list[k]'s three blobs (the input of the exclusive scan that places them)
+void launch_canon_len(const kwok_node_event* ev, const uint32_t* list, uint32_t n, uint64_t* lens, hipStream_t st);
+struct CanonArgs {
+    const uint8_t* arena;        // the documents the scanner read (never written)
+    kwok_node_event* ev;         // the batch's records: raw blob spans; an unclean document's record is cleared
+    int32_t* status;             // ... and its status becomes JSON_HOST
+    const uint32_t* list;        // [n] the canon list
+    uint32_t n;
+    const uint64_t* off;         // [n] the exclusive scan of lens: where list[k]'s blobs go in out
+    uint8_t* out;                // the compact canonical bytes
+    CanonDoc* docs;              // [n] out
+    uint32_t* host_list;         // the scanner's host list: an unclean document is appended
+    uint32_t* n_host;
+};
+void launch_canon(const CanonArgs& A, hipStream_t st);
+// out[k] = in[0] + ... + in[k - 1] (rocPRIM, refs.hip; tmp of refs_scan_bytes(n))
+int launch_scan64(const uint64_t* in, uint64_t* out, uint32_t n, void* tmp, size_t tmp_bytes, hipStream_t st);
 void launch_node_gather(const kwok_node_event* ev, const uint32_t* list, uint32_t n, kwok_node_event* out, hipStream_t st);
 void launch_node_scatter(kwok_node_event* ev, const kwok_node_event* in, const uint32_t* list, uint32_t n, hipStream_t st);
 void launch_json_gather(const kwok_pod_event* ev, const JsonPodSide* side, const uint32_t* list, uint32_t n,

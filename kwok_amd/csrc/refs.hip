@@ -340,6 +340,13 @@ int launch_refs_scan(const RefQuery& Q, void* tmp, size_t tmp_bytes, hipStream_t
                ? KWOK_OK
                : KWOK_EDEVICE;
 }
+// the same scan over any sizes (the node status blob canonicaliser places its blobs with it)
+int launch_scan64(const uint64_t* in, uint64_t* out, uint32_t n, void* tmp, size_t tmp_bytes, hipStream_t st) {
+    if (!n) return KWOK_OK;
+    return rocprim::exclusive_scan(tmp, tmp_bytes, in, out, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), st) == hipSuccess
+               ? KWOK_OK
+               : KWOK_EDEVICE;
+}
 void launch_refs_gather(const DevState& S, const RefDir& R, const RefQuery& Q, const uint32_t* slots, hipStream_t st) {
     if (Q.n)
         hipLaunchKernelGGL(k_refs_gather, dim3(cdiv((uint64_t)Q.n * REF_GATHER_LANES, 256)), dim3(256), 0, st, S, R, Q, slots);

@@ -149,6 +149,8 @@ def declare(lib, pre):
             "frame_responses_gpu": (C.c_int, [VP, VP, SZ, VP, VP, SZ, VP, P(SZ), P(U64)]),
             "echo_note_framed": (C.c_int, [VP, U64, VP, SZ, VP]),
             "response_stats": (C.c_int, [VP, VP]),
+            "canon_enable": (C.c_int, [VP, C.c_int]),
+            "canon_stats": (C.c_int, [VP, VP]),
         })
     for name, (res, args) in sig.items():
         f = getattr(lib, pre + name, None)
@@ -891,6 +893,19 @@ class Engine(EngineBase):
         out = (C.c_uint64 * len(abi.RESP_STATS))()
         self._check(self._lib.kwok_response_stats(self._h, out), "response_stats")
         return dict(zip(abi.RESP_STATS, list(out)))
+
+    # ---- node status blobs canonicalised on the GPU (include/kwok_canon.h) ----
+    def canon_enable(self, on=True):
+        """kwok_canon_enable: the device writes the canonical addresses / allocatable / capacity of every node
+        document whose blobs are inside its domain; the host codec decodes only the others (idempotent)"""
+        self._check(self._lib.kwok_canon_enable(self._h, 1 if on else 0), "canon_enable")
+
+    def canon_stats(self):
+        """kwok_canon_stats: documents / blobs canonicalised, raw and canonical bytes, documents sent to the host
+        because a blob was outside the device domain, decode calls that launched the canon kernels"""
+        out = (C.c_uint64 * len(abi.CANON_STATS))()
+        self._check(self._lib.kwok_canon_stats(self._h, out), "canon_stats")
+        return dict(zip(abi.CANON_STATS, list(out)))
 
     # ---- the pod and node reference directory (include/kwok_watch.h): what a patch is addressed to ----
     def refs_enable(self):
